@@ -3,14 +3,18 @@ bf16 train step, batch 64 per GPU, 224x224 images, seq_len 64), one process per 
 (configs[3]) as `beam4_generate`.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full              # + every leg beside the headline (below)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR  # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus 8 ...            # starts its own 8 ranks (torch.distributed.run as a CHILD process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = forward + loss + backward + gradient all-reduce (RCCL, N > 1) + AdamW on synthetic data (random-init weights of
-the full architecture; fused dropout active as in training).  Prints ONE JSON line on rank 0.
+the full architecture; fused dropout active as in training).  Prints ONE JSON line on rank 0.  A plain run sets up, warms up,
+times --steps steps and prints the line; the legs beside the headline (host issue time, h2d_inclusive, dense_captions, roofline,
+beam4_generate, cpu_baseline, comm_emulated, fp8_train) run with --full only and are null without it.
 Variants: --dtype fp8 (configs[4]: e4m3/e5m2 QKV / FFN / LM-head GEMMs), --dense-captions (n = 62 tokens in every caption: no padded
 label positions, the dense upper bound of SURVEY §8d), --pmc-traffic (re-measure roofline.traffic with two rocprofv3
-counter passes of this same command as child processes).  With --gpus 1 the line also carries `comm_emulated`: the same step
+counter passes of this same command as child processes; with --full).  With --gpus 1 --full the line also carries `comm_emulated`: the same step
 with the gradient exchange among 2 / 4 / 8 ranks EMULATED on this one GPU (a kernel holding 32 CUs of a CU-masked collective
 stream for the projected all-reduce time of every bucket; one fresh child process per N) — a scheduling probe, not a scaling
 result; --emulate-comm '' switches it off, --emulate-main N makes the timed trainer itself emulate (profiling aid).
@@ -358,9 +362,9 @@ def pmc_traffic(argv, kernel_prefix="gemm_"):
     for a in argv:
         if skip:
             skip = False
-        elif a in ("--gpus", "--steps", "--warmup", "--emulate-comm"):
+        elif a in ("--gpus", "--steps", "--warmup", "--emulate-comm", "--dump-outputs"):
             skip = True
-        elif a != "--pmc-traffic" and not a.startswith(("--gpus=", "--steps=", "--warmup=", "--emulate-comm=")):
+        elif a != "--pmc-traffic" and not a.startswith(("--gpus=", "--steps=", "--warmup=", "--emulate-comm=", "--dump-outputs=")):
             child_argv.append(a)
     for ctr, factor in (("FETCH_SIZE", 2.0), ("WRITE_SIZE", 1.0)):
         d = tempfile.mkdtemp(prefix="mic_pmc_", dir="/tmp")
@@ -381,7 +385,51 @@ def pmc_traffic(argv, kernel_prefix="gemm_"):
     return (tot / launches, launches / 2) if launches else (None, 0)
 
 
-def main():
+def dump_outputs(path, out, store, per_leaf=4096, seed=0):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as float32 .npy files — the step's metrics
+    (`loss`, `learning_rate`) and the trainer state the step updated (`params`: fp32 master weights, `adam_m` / `adam_v`: AdamW
+    moments), the latter as a fixed, seeded sample of every parameter leaf in the Flax layout (leaves in sorted order, up to
+    `per_leaf` positions each, ~9 MB per array at full size): independent of the store's internal packing, so two builds compare
+    element for element."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for k in ("loss", "learning_rate"):
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray(out[k].detach().float().cpu()).reshape(1))
+    shapes = store.flax_shapes()
+    for name, source in (("params", "master"), ("adam_m", "m"), ("adam_v", "v")):
+        leaves = {}
+        for seg_name, parts in store._mapping():  # the device-side counterpart of ParamStore.export_flat: views in the Flax layout
+            src = store._seg_view(source, seg_name).detach()
+            r0 = 0
+            for leaf, tr in parts:
+                shp = shapes[leaf]
+                if tr == "T":
+                    n = shp[1]
+                    t = src[r0: r0 + n].T
+                elif tr == "conv":
+                    n = shp[-1]
+                    t = src[r0: r0 + n].T.reshape(shp)
+                elif tr in ("flb", "pad_rows"):
+                    n = store.V
+                    t = src[: store.V]
+                else:
+                    n = shp[0]
+                    t = src[r0: r0 + n]
+                leaves[leaf] = t.reshape(-1)
+                r0 += n
+        rng = np.random.default_rng(seed)
+        parts_out = []
+        for leaf in sorted(leaves):
+            flat = leaves[leaf]
+            numel = flat.numel()
+            idx = np.arange(numel) if numel <= per_leaf else np.sort(rng.integers(0, numel, per_leaf))
+            parts_out.append(flat[torch.from_numpy(idx).to(flat.device)].float().cpu())
+        np.save(os.path.join(path, f"{name}.npy"), torch.cat(parts_out).numpy())
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -392,7 +440,7 @@ def main():
                     help="gradient exchange precision for --gpus > 1: fp32 (default) = the reference's pmean (main.py:698); bf16 = half the xGMI "
                          "bytes, opt-in; auto = bf16 where the PROJECTED fp32 all-reduce would not hide under backward (N = 2, 4: "
                          "mic_amd.train.choose_comm_dtype), fp32 elsewhere")
-    ap.add_argument("--emulate-comm", default=None, help="(default 2,4,8; off for --small) ""world sizes whose gradient exchange is EMULATED on this one GPU after the timed region "
+    ap.add_argument("--emulate-comm", default=None, help="(default 2,4,8 with --full; off for --small and without --full) ""world sizes whose gradient exchange is EMULATED on this one GPU after the timed region "
                     "(a kernel holding --comm-cus CUs for the projected all-reduce time of every bucket): reported as `comm_emulated`, a "
                     "scheduling probe, not a scaling result; '' or 0 = off; only with --gpus 1")
     ap.add_argument("--emulate-main", type=int, default=0, help="profiling aid: the TIMED trainer itself runs with the emulated exchange among N ranks "
@@ -411,9 +459,27 @@ def main():
                     "(h2d_inclusive) leg, no fp8 leg) — the step count of a kernel trace is then exactly warmup + steps")
     ap.add_argument("--gen-batch", type=int, default=256)
     ap.add_argument("--generate-only", action="store_true", help="profiling aid: only the beam-4 leg")
-    ap.add_argument("--pmc-traffic", action="store_true", help="measure roofline.traffic now (two rocprofv3 child passes, ~2 min)")
+    ap.add_argument("--pmc-traffic", action="store_true", help="(with --full) measure roofline.traffic now (two rocprofv3 child passes, ~2 min)")
     ap.add_argument("--small", action="store_true", help="reduced model (debug only; result is NOT the benchmark)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="every figure beside the headline: host issue time, h2d_inclusive, dense_captions, "
+                    "roofline, the beam-4 leg, the CPU baselines, the emulated-exchange legs and the fp8 leg (the --no-* options switch single "
+                    "ones off).  Without it a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(loss, learning rate, a seeded sample of the updated weights and AdamW moments) as DIR/<name>.npy, float32")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: only what the headline needs
+        args.no_cpu_baseline = args.no_roofline = args.no_generate = args.no_dense_leg = args.no_fp8_leg = args.no_extra_legs = True
+        if args.emulate_comm is None:
+            args.emulate_comm = ""
+        if args.pmc_traffic:
+            ap.error("--pmc-traffic measures roofline.traffic, a --full figure: add --full")
+    if args.dump_outputs is not None and args.generate_only:
+        ap.error("--dump-outputs writes the train step's outputs; --generate-only runs no train step")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
@@ -536,6 +602,10 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     images_per_sec = world * B * args.steps / dt
+    # the outputs of the last timed step, before any further step (the --full legs below) moves the trainer's state on
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, out, model.store)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # host time to ISSUE one step with the GPU idle (queue empty at the start: no back-pressure; `host_loop_ms_per_step` above is the
     # figure of a loop whose queue is full, i.e. it mostly measures the GPU): median of 3, each behind a device sync
@@ -657,7 +727,7 @@ def main():
                      "projected_allreduce_ms_fp32": round(allreduce_ms(4.0 * model.store.numel, args.emulate_main), 2)}
 
     if rank == 0:
-        note(f"{images_per_sec:.1f} images/s; roofline step")
+        note(f"{images_per_sec:.1f} images/s" + ("; roofline step" if not args.no_roofline else ""))
     roofline = None
     peak = PEAK_TFLOPS[args.dtype]
 
@@ -766,7 +836,7 @@ def main():
     if world > 1:
         dist.barrier()
 
-    if rank == 0:
+    if rank == 0 and not args.no_generate:
         note("beam-4 leg")
     gen = None
     if not args.no_generate:
@@ -831,7 +901,7 @@ def main():
         drop = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "ROLE_WORLD_SIZE", "GROUP_WORLD_SIZE")
         env = {k: v for k, v in os.environ.items() if k not in drop and not k.startswith(("MASTER_", "TORCHELASTIC_"))}
         cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "fp8", "--steps", str(args.steps), "--warmup", str(max(args.warmup, 3)), "--no-generate",
-               "--no-cpu-baseline", "--no-dense-leg", "--no-extra-legs", "--emulate-comm", "0", "--batch", str(args.batch)] + (["--no-roofline"] if args.no_roofline else [])
+               "--no-cpu-baseline", "--no-dense-leg", "--no-extra-legs", "--emulate-comm", "0", "--batch", str(args.batch), "--full"] + (["--no-roofline"] if args.no_roofline else [])
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             cd = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

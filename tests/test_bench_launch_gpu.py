@@ -13,11 +13,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra, env_extra=None, timeout=600):
+def _run(extra, env_extra=None, timeout=600, full=True):
+    """the legs these tests look at (roofline, beam-4, dense captions, emulated exchange, host figures) run with --full only"""
     env = dict(os.environ, **(env_extra or {}))
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--small", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra,
-                       env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--small", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+                       + (["--full"] if full else []) + extra, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     return r
 
 
@@ -89,3 +90,32 @@ def test_bench_fp8_line(dev):
     assert d["dtype"] == "fp8" and d["config"]["workload"].startswith("configs[4]") and "e4m3" in d["config"]["gemm_dtype"]
     assert d["roofline"]["peak"] == 5000.0 and d["roofline"]["fp8_gemms"]["launches_per_step"] > 0 and d["fp8_train"] is None
     assert abs(d["final_loss"]) < 100
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(dev, tmp_path):
+    """without --full: set-up, warm-up, the --steps timed steps and the line (every leg beside the headline null); --dump-outputs
+    writes what the last timed step computed as float32 .npy files, the same from run to run (same arguments, same inputs)"""
+    import numpy as np
+
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        r = _run(["--steps", "3", "--dump-outputs", str(out)], full=False)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "images/sec"
+        assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["n_gpus"] == 1
+        for k in ("host_issue_ms_per_step", "h2d_inclusive", "dense_captions", "roofline", "beam4_generate", "cpu_baseline", "comm_emulated",
+                  "fp8_train", "emulation"):
+            assert d[k] is None, k
+        files = {f.name[:-4]: np.load(f) for f in out.glob("*.npy")}
+        assert set(files) == {"loss", "learning_rate", "params", "adam_m", "adam_v"}, sorted(files)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert sum(a.nbytes for a in files.values()) < 64 << 20
+        assert abs(float(files["loss"][0]) - d["final_loss"]) < 1e-3 and float(files["learning_rate"][0]) > 0
+        assert files["params"].shape == files["adam_m"].shape == files["adam_v"].shape and (files["adam_v"] > 0).any()
+        dumps.append(files)
+    for k, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][k], a, rtol=1e-3, atol=1e-3 * float(np.abs(a).max()), err_msg=k)

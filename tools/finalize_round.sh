@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; RD=${ROUND:-r6}; export ROUND=$RD; O=$R/gpurun_out/${RD}final; mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q -rP 2>&1 | grep -E "^\[|passed|failed|skipped|Error" | grep -v "Gloo\|W1002\|socket" > $O/pytest_gpu.log
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 # same-box A/B of the two GEMM modes (two interleaved pairs)
 for i in 1 2; do for d in bf16 fp8; do echo "$d $(python bench.py --dtype $d --steps 20 --warmup 5 --no-generate --no-cpu-baseline --no-roofline --no-dense-leg --no-extra-legs --emulate-comm 0 2>/dev/null | grep '^{' | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], "ms", d["value"], "images/s")')"; done; done > $O/${RD}_ab_bf16_vs_fp8.txt
 python tools/h2d_probe.py > $O/${RD}_h2d_probe.txt 2>/dev/null
