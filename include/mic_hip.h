@@ -61,10 +61,16 @@ const char* mic_last_error(void);
  *   Linear dX   dx = dy W      : a_kmajor=0, b_kmajor=1
  *   Linear dW   dW = dy^T x    : a_kmajor=1, b_kmajor=1
  * epilogue, in this order (each optional):
- *   v = acc (+ bias[n]);  Zout[m,n] = v (pre-activation, saved for backward);  v = act(v);
+ *   v = acc * alpha (+ bias[n]);  Zout[m,n] = v (pre-activation, saved for backward);  v = act(v rounded to the Zout dtype: what
+ *   backward reads back; also without Zout);
  *   v *= act'(Zin[m,n]) (activation backward);  v = dropout(v; seed, p, index m*N+n);
  *   v += R[m,n];  v += C_old[m,n] (accumulate);  C[m,n] = v  (c_dtype)
  * Requirements: K % 64 == 0 for MIC_BF16 (callers zero-pad the reduction dimension); lda/ldb % 8 == 0 (bf16).
+ * C / Zout / Zin / R may start at any element offset and have any leading dimension: the epilogue stores 16-B vectors only where
+ * the leading dimensions are multiples of 8 AND the base addresses are 16-B aligned, elementwise otherwise.  Exceptions, refused
+ * with MIC_EINVAL when misaligned: the features that exist on the vector path only — an fp8 C (8-B aligned C, 16-B aligned
+ * Zout / Zin / R), rowstat (16-B aligned C), the folded LayerNorm (16-B aligned C / R / Zout), rowsum2 (16-B aligned C / R) — and
+ * split-K slabs (a 16-B aligned workspace, split_stride % 4 == 0).
  * bf16 path: LDS-staged 64x64x64, 128x128x64 or 256x256x64 tiles (operands through registers into XOR-swizzled LDS images),
  * v_mfma_f32_32x32x16_bf16, k-major operands through ds_read_b64_tr_b16.  f32 path: v_mfma_f32_32x32x2_f32 (exact fp32).
  * ------------------------------------------------------------------------------------------- */
@@ -134,7 +140,7 @@ typedef struct {
 } mic_gemm_args;
 int mic_gemm(const mic_gemm_args* a, void* stream);
 /* dst[r][c] (dst_dtype) = sum over s < n_slabs of src[s * slab_stride + r * ld_src + c] (fp32): the second half of a
- * workspace split-K GEMM. */
+ * workspace split-K GEMM.  16-B vectors: src and dst 16-B aligned, cols % 8 == 0, ld_src % 4 == 0, ld_dst % 8 == 0. */
 int mic_sum_slabs(int dst_dtype, int n_slabs, long long slab_stride, int rows, int cols, const float* src, int ld_src,
                   void* dst, int ld_dst, void* stream);
 /* `count` GEMMs that share dtype and operand layouts in as few launches as possible (one launch per 8 problems):

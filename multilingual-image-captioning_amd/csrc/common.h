@@ -291,6 +291,7 @@ __device__ __forceinline__ float act_bwd(int act, float x) {
 struct EpiArgs {
   void* C; int ldc; int c_f32;
   const float* bias; int act;
+  int vec;  // 1: the 16-B vector epilogue may touch C / Zout / Zin / R (leading dimensions AND base addresses aligned; fill_epi)
   void* Zout; int ldz;
   const void* Zin; int dact;
   const void* R; int ldr;
@@ -337,9 +338,9 @@ __device__ __forceinline__ void unpack8(u32x4 u, float* o) {
   o[4] = __uint_as_float(u.z << 16); o[5] = __uint_as_float(u.z & 0xffff0000u);
   o[6] = __uint_as_float(u.w << 16); o[7] = __uint_as_float(u.w & 0xffff0000u);
 }
-__device__ __forceinline__ bool epilogue_vec_ok(const EpiArgs& e, int cnt) {
-  return cnt == 8 && (e.ldc & 7) == 0 && (!e.Zout || (e.ldz & 7) == 0) && (!e.Zin || (e.ldz & 7) == 0) && (!e.R || (e.ldr & 7) == 0);
-}
+// The 16-B vector path needs the base addresses aligned as well as the leading dimensions: a C / Z / R that starts mid-vector
+// (a column-offset view) takes the scalar path.  The host decides it once per problem (EpiArgs::vec).
+__device__ __forceinline__ bool epilogue_vec_ok(const EpiArgs& e, int cnt) { return cnt == 8 && e.vec; }
 #define MIC_ROWSUM_SCALE 1048576.0f            /* 2^20: |sum of squares| up to 8.8e12 fits an int64 */
 #define MIC_ROWSUM_INV_SCALE 9.5367431640625e-7f /* 2^-20 */
 // LayerNorm folded around the GEMM: v[i] = acc of x . (gamma o W)^T for row m, columns n .. n+7  ->  LN(x) . W^T + bias'
@@ -439,12 +440,10 @@ __device__ __forceinline__ void epilogue_store8_pre(const EpiArgs& e, int m, int
 }
 
 // 8 consecutive columns [n, n+cnt) of row m.  Vector (16-B) path when all 8 are in range and every touched pointer is
-// 16-B aligned; scalar fallback otherwise.
+// 16-B aligned (leading dimensions and base addresses: epilogue_vec_ok); scalar fallback otherwise.
 template <typename T>
 __device__ __forceinline__ void epilogue_store8(const EpiArgs& e, int m, int n, float* v, int cnt) {
-  const bool vec = cnt == 8 && (e.ldc & 7) == 0 && (!e.Zout || (e.ldz & 7) == 0) && (!e.Zin || (e.ldz & 7) == 0) &&
-                   (!e.R || (e.ldr & 7) == 0);
-  if (!vec) {
+  if (!epilogue_vec_ok(e, cnt)) {
     for (int i = 0; i < cnt; ++i) epilogue_store<T>(e, m, n + i, v[i]);
     return;
   }

@@ -1031,6 +1031,7 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(int n_slabs, long slab_s
 }
 extern "C" int mic_sum_slabs(int dst_dtype, int n_slabs, long long slab_stride, int rows, int cols, const float* src, int ld_src,
                              void* dst, int ld_dst, void* stream) {
+  MIC_CHECK(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0, "mic_sum_slabs: src and dst must be 16-B aligned (16-B vector reads and writes)");
   MIC_CHECK(n_slabs > 0 && rows > 0 && cols > 0 && cols % 8 == 0 && ld_src % 4 == 0 && ld_dst % 8 == 0 && slab_stride % 4 == 0 && src && dst,
             "mic_sum_slabs: bad args");
   const long total = (long)rows * (cols >> 3);

@@ -96,6 +96,7 @@ static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
       MIC_CHECK((a->act || a->dact || a->Zout) && !a->accumulate && a->split_k <= 1 && !a->a_kmajor, "mic_gemm(fp8 C): an activation / dact epilogue of an NT launch, no accumulate / split-K");
       MIC_CHECK(a->N % 8 == 0 && a->ldc % 8 == 0 && ((uintptr_t)a->C & 7) == 0 && (!a->Zout || a->ldz % 8 == 0) && (!a->Zin || a->ldz % 8 == 0) && (!a->R || a->ldr % 8 == 0),
                 "mic_gemm(fp8 C): N, ldc, ldz, ldr multiples of 8");
+      MIC_CHECK((((uintptr_t)a->Zout | (uintptr_t)a->Zin | (uintptr_t)a->R) & 15) == 0, "mic_gemm(fp8 C): Zout / Zin / R must be 16-B aligned (the emission has no scalar path)");
     }
     MIC_CHECK(a->a_kmajor == a->b_kmajor, "mic_gemm(fp8): both operands k-contiguous (NT) or both k-major (TN, the weight-gradient GEMM)");
     if (a->a_kmajor) MIC_CHECK(a->M % 16 == 0 && a->N % 16 == 0, "mic_gemm(fp8, k-major): M and N must be multiples of 16");
@@ -115,6 +116,10 @@ static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
   e.C = a->C; e.ldc = a->ldc; e.c_f32 = (a->c_dtype == MIC_F32);
   e.c_q8 = a->c_dtype == MIC_FP8 ? 1 + a->c_q8_fmt : 0; e.q8_state = a->c_q8_state; e.q8_amax = a->c_q8_amax;
   e.bias = a->bias; e.act = a->act; e.Zout = a->Zout; e.ldz = a->ldz; e.Zin = a->Zin; e.dact = a->dact;
+  // 16-B vector epilogue: leading dimensions multiples of 8 and every touched base address aligned (an fp8 C is written 8 bytes at
+  // a time); anything else takes the elementwise path
+  e.vec = a->ldc % 8 == 0 && (!(a->Zout || a->Zin) || a->ldz % 8 == 0) && (!a->R || a->ldr % 8 == 0) &&
+          (((uintptr_t)a->Zout | (uintptr_t)a->Zin | (uintptr_t)a->R) & 15) == 0 && ((uintptr_t)a->C & (a->c_dtype == MIC_FP8 ? 7 : 15)) == 0;
   e.R = a->R; e.ldr = a->ldr; e.accumulate = a->accumulate;
   e.drop_thr = a->dropout_p > 0.f ? (uint32_t)fminf(a->dropout_p * 4294967296.0f, 4294967295.0f) : 0u;
   e.drop_seed = a->dropout_seed; e.drop_scale = 1.0f / (1.0f - a->dropout_p);
@@ -132,8 +137,10 @@ static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
   if (a->a_ln_stats) {
     MIC_CHECK(a->dtype == MIC_BF16 && a->a_ln_colsum && a->bias && a->a_ln_width > 0, "mic_gemm: a folded LayerNorm needs bf16 operands, a_ln_colsum, bias' and a_ln_width");
     MIC_CHECK(a->split_k <= 1 && !a->dact && !a->accumulate && (a->alpha == 0.f || a->alpha == 1.f), "mic_gemm: folded LayerNorm: no split-K / dact / accumulate / alpha");
-    MIC_CHECK(a->N % 8 == 0 && a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 && (!a->R || a->ldr % 8 == 0) && (!a->Zout || a->ldz % 8 == 0),
-              "mic_gemm: folded LayerNorm needs the vector epilogue (N, ldc, ldr, ldz multiples of 8, 16-B aligned C)");
+    // (the elementwise epilogue path has no folded LayerNorm: every pointer the vector path touches must allow it)
+    MIC_CHECK(a->N % 8 == 0 && a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 && (!a->R || a->ldr % 8 == 0) && (!a->Zout || a->ldz % 8 == 0) &&
+                  (((uintptr_t)a->R | (uintptr_t)a->Zout) & 15) == 0,
+              "mic_gemm: folded LayerNorm needs the vector epilogue (N, ldc, ldr, ldz multiples of 8, 16-B aligned C / R / Zout)");
     e.ln_bias = a->bias; e.bias = nullptr; e.ln_inv_d = 1.0f / (float)a->a_ln_width;
   }
   if (a->rowsum2) {
@@ -325,7 +332,10 @@ static int launch_bf16(const mic_gemm_args* args, int count, hipStream_t s) {
     p.split_stride = p.nsplit > 1 ? args[i].split_stride : 0;
     MIC_CHECK(args[i].split_stride >= 0 && (args[i].split_stride == 0 || args[i].split_stride >= (long long)(p.M - 1) * args[i].ldc + p.N),
               "mic_gemm: split_stride must cover one M x N slab");
-    MIC_CHECK(p.split_stride == 0 || p.nsplit == args[i].split_k, "mic_gemm: split_k exceeds K/64 with a slab workspace");
+    // (tested on the arguments: with split_k clamped to 1 the launch would fill slab 0 alone and leave the others to the caller's sum)
+    MIC_CHECK(args[i].split_k <= 1 || args[i].split_stride == 0 || p.nsplit == args[i].split_k, "mic_gemm: split_k exceeds K/64 with a slab workspace");
+    MIC_CHECK(p.split_stride % 4 == 0 && (p.split_stride == 0 || ((uintptr_t)args[i].C & 15) == 0),
+              "mic_gemm: a split-K slab workspace is 16-B aligned with split_stride %% 4 == 0 (mic_sum_slabs reads it as 16-B vectors)");
     MIC_CHECK(!args[i].a_rowsum || args[i].a_kmajor, "mic_gemm: a_rowsum needs a_kmajor (A = dy^T of the weight-gradient GEMM)");
     p.a_rowsum = args[i].a_rowsum;
     p.rowsum_k = args[i].rowsum_k > 0 ? args[i].rowsum_k : p.K;
@@ -336,8 +346,11 @@ static int launch_bf16(const mic_gemm_args* args, int count, hipStream_t s) {
     blocks += p.tiles_m * p.tiles_n * p.nsplit;
   }
   tab.total_blocks = blocks;
-  for (int i = 0; i < count; ++i)
+  for (int i = 0; i < count; ++i) {
     MIC_CHECK(!args[i].rowsum2 || table_is_plain(tab), "mic_gemm_grouped: rowsum2 needs every problem of the launch on the bare / residual epilogue");
+    // (the softmax partials are written by the PLAIN epilogue and by gemm_w4 / gemm_d2, which take single-problem launches only)
+    MIC_CHECK(!args[i].rowstat || table_is_plain(tab), "mic_gemm_grouped: rowstat needs every problem of the launch on the bare / residual epilogue");
+  }
   // The two-blocks-per-CU 256 x 128 kernel (gemm_d2.hip) takes the four-wave kernel's launches that carry softmax partials (the
   // LM-head forward: K = 1024 tiles whose epilogue is a third of their time — under a second block's MFMAs it is cover).  Its K loop
   // is slower than the four-wave kernel's (64-B DMA segments: bound by L2 requests), so the deep-K and bare launches stay there.

@@ -306,6 +306,7 @@ bool gemm_d2_takes(const LaunchTable& tab) {
   if ((e.Zout || e.Zin) && ((e.ldz & 7) != 0 || ((uintptr_t)(e.Zout ? e.Zout : e.Zin) & 15) != 0)) return false;
   if (e.R && ((e.ldr & 7) != 0 || ((uintptr_t)e.R & 15) != 0)) return false;
   if (e.dact && e.accumulate && !e.c_f32) return false;  // (epilogue_pre_ok)
+  if (!e.vec) return false;  // its side loads are 16-B vectors: every leading dimension and base address aligned (fill_epi)
   if (p.nsplit > 1 && !(e.c_f32 && p.split_stride > 0)) return false;
   if (e.rowstat && (e.c_f32 || e.act || e.Zout || e.dact || e.R || e.drop_thr || e.accumulate)) return false;
   return true;

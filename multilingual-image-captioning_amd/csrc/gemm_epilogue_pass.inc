@@ -120,7 +120,7 @@
         float* c = (float*)E.C + (size_t)m * E.ldc + n;
         if (split_stride > 0) {
           c += (size_t)split * (size_t)split_stride;
-          if (cnt == 8 && (E.ldc & 3) == 0) st8(c, v);
+          if (cnt == 8 && (E.ldc & 3) == 0) st8(c, v);  // (host side: a slab workspace is 16-B aligned)
           else for (int i = 0; i < cnt; ++i) c[i] = v[i];
         } else {
           for (int i = 0; i < cnt; ++i) atomicAdd(c + i, v[i]);

@@ -1,12 +1,28 @@
 """Per-kernel summary (count, total, average, share) from a rocprofv3 rocpd SQLite database or kernel-trace CSV."""
 import csv
+import functools
 import re
 import sqlite3
 import sys
 from collections import defaultdict
 
 
+@functools.lru_cache(maxsize=None)
+def demangle(name):
+    """rocpd databases may hold the mangled symbol ("_Z...EEv11LaunchTable.kd"): demangle through c++filt when it is there"""
+    if not name.startswith("_Z"):
+        return name
+    import shutil
+    import subprocess
+
+    tool = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    if tool is None:
+        return name
+    return subprocess.run([tool, re.sub(r"\.kd$", "", name)], capture_output=True, text=True).stdout.strip() or name
+
+
 def short(name):
+    name = demangle(name)
     name = re.sub(r"^void ", "", name)
     name = name.replace("(anonymous namespace)::", "")
     name = re.sub(r"\(.*", "", name)
