@@ -150,17 +150,26 @@ int mic_gemm_grouped(const mic_gemm_args* args, int count, void* stream);
  * MIC_FREE_CUS from the environment).  The planner sizes "one round" launches (one 16-wave block with two / four K-groups per CU)
  * and persistent grids for this number; a data-parallel job lowers it by the CUs its collectives occupy — the reference's
  * `lax.pmean` (main.py:698) is scheduled by XLA inside the step, here RCCL's channel blocks sit on CUs of their own beside backward —
- * so that a launch sized for 256 free CUs re-plans instead of spilling a few blocks into a second round.  Process-wide. */
+ * so that a launch sized for 256 free CUs re-plans instead of spilling a few blocks into a second round.  THREAD-LOCAL (see the
+ * conventions above): it belongs to the calling thread's later mic_gemm* / mic_gemm_plan calls. */
 int mic_set_cu_budget(int cus);
 int mic_get_cu_budget(void);
 /* What mic_gemm_grouped would launch for these problems under the current CU budget (host arithmetic only, nothing is launched;
- * pointers in `args` are not dereferenced): tile edge (256 / 128 / 64; `tile_m` x `tile` when the rows differ), K-groups per block, logical blocks, launched grid
- * (persistent launches: the budget), blocks of this configuration that fit one CU, and whether the LDS-DMA phased kernel is taken
- * (phased = 1; 2 = the shape fits the four-wave kernel gemm_w4.hip — on by default, MIC_GEMM_W4=0 switches it off — which takes the launch
- * if its epilogue is a bare one: bf16 C with bias / folded LayerNorm / softmax partials, or fp32 C, also as split-K slabs; of those
- * the launches WITH softmax partials run on the two-blocks-per-CU 256 x 128 kernel gemm_d2.hip, MIC_GEMM_D2=0 switches that off — for
- * args that carry `rowstat` the plan reports that tiling: tile 128, tile_m 256, blocks_per_cu 2). */
-typedef struct { int tile, kgroups, blocks, grid, blocks_per_cu, phased, cu_budget, tile_m; } mic_gemm_plan_info;  /* tile_m: tile rows (= tile, or 192 with tile 128) */
+ * pointers in `args` are not dereferenced; argument sets mic_gemm would refuse are still answered).  The launcher and this report
+ * read ONE decision (csrc/gemm.hip: decide), so the report names the kernel that runs:
+ *   family: 0 = 64x64 tiles, 1 = 128x128, 2 = 192x128, 3 = 256x256 (all gemm_kernel.h, register-staged), 4 = the LDS-DMA four-phase
+ *           256x256 kernel (gemm_phased.hip), 5 = the four-wave 256x256 kernel (gemm_w4.hip: bf16 NT launches whose epilogue is a
+ *           bare one — bf16 C with bias / folded LayerNorm / softmax partials, or fp32 C, also as split-K slabs; MIC_GEMM_W4=0
+ *           switches it off), 6 = the two-blocks-per-CU 256x128 kernel (gemm_d2.hip: by default those of the four-wave kernel's
+ *           launches that carry softmax partials; MIC_GEMM_D2);
+ *   plain:  1 = every problem on the bare / residual epilogue (the PLAIN instantiation of families 0-4);
+ *   epi:    the epilogue instantiation of family 5 (gemm_w4_kernel<2|3|6|7|8>) and 6 (gemm_d2_kernel<0|1>), 0 otherwise;
+ *   tile_m x tile: tile rows x columns (64 / 128 / 256 square, 192 x 128, 256 x 128 for family 6); K-groups per block; logical
+ *   blocks; launched grid (persistent launches — PLAIN family 3 with more tiles than CUs —: the budget); blocks of this
+ *   configuration that fit one CU;
+ *   phased: kept for older callers — 0, 1 = the SHAPE fits family 4, 2 = the shape fits family 5; the epilogue is not looked at
+ *           there, `family` says what runs. */
+typedef struct { int tile, kgroups, blocks, grid, blocks_per_cu, phased, cu_budget, tile_m, family, plain, epi; } mic_gemm_plan_info;
 int mic_gemm_plan(const mic_gemm_args* args, int count, mic_gemm_plan_info* out);
 /* Operands of a LayerNorm-folded Linear (see mic_gemm_args.a_ln_stats): for w [N][K] (the compute-dtype weight), gamma / beta
  * fp32 [K], bias fp32 [N] or NULL:  w_fold[n][k] = round(w[n][k] * gamma[k]),  colsum[n] = sum_k w_fold[n][k] (of the ROUNDED

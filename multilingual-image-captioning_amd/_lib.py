@@ -67,7 +67,10 @@ class BeamStepArgs(C.Structure):
 
 class GemmPlanInfo(C.Structure):
     _fields_ = [("tile", C.c_int), ("kgroups", C.c_int), ("blocks", C.c_int), ("grid", C.c_int), ("blocks_per_cu", C.c_int),
-                ("phased", C.c_int), ("cu_budget", C.c_int), ("tile_m", C.c_int)]
+                ("phased", C.c_int), ("cu_budget", C.c_int), ("tile_m", C.c_int), ("family", C.c_int), ("plain", C.c_int), ("epi", C.c_int)]
+
+
+GEMM_FAMILIES = ("t64", "t128", "t192", "t256", "phased", "w4", "d2")  # GemmPlanInfo.family (include/mic_hip.h)
 
 
 class LnParamItem(C.Structure):

@@ -1,7 +1,9 @@
-// gemm.hip — MFMA GEMMs with fused epilogues (mic_gemm / mic_gemm_grouped): argument checks, launch-table construction and the
-// choice of tile configuration.  The bf16 / fp8 kernel template itself is gemm_kernel.h, instantiated in gemm_t256.hip /
-// gemm_t128.hip / gemm_t64.hip (one translation unit per tile configuration, so they compile in parallel); the fp32 kernel
-// is below.
+// gemm.hip — MFMA GEMMs with fused epilogues (mic_gemm / mic_gemm_grouped): argument checks (check_epi, check_table), launch-table
+// construction (fill_table, tile_table), the latched A/B switches (GemmSwitches) and THE dispatch decision (`decide`: kernel family,
+// tiling, K-groups, PLAIN, epilogue instantiation, grid) that launch_bf16 launches and mic_gemm_plan reports — no other file chooses.
+// The bf16 / fp8 kernel template itself is gemm_kernel.h, instantiated in gemm_t256.hip / gemm_t192.hip / gemm_t128.hip /
+// gemm_t64.hip (one translation unit per tile configuration, so they compile in parallel); gemm_phased.hip, gemm_w4.hip and
+// gemm_d2.hip hold the LDS-DMA kernels (the latter two say which epilogues they take: gemm_*_takes); the fp32 kernel is below.
 //
 // bf16 kernel: ONE template, table-driven (a launch carries up to 8 problems), three tile configurations chosen per launch:
 //   256x256 tile, 8 waves (2x4), wave tile 128x64 (4x2 v_mfma_f32_32x32x16_bf16 accumulators), 128 KiB LDS, 1 block/CU
@@ -84,7 +86,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
   }
 }
 
-static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
+// the host checks of one problem (every dtype): what include/mic_hip.h promises to refuse
+static int check_epi(const mic_gemm_args* a) {
   MIC_CHECK(a && a->A && a->B && a->C, "mic_gemm: null pointer");
   MIC_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "mic_gemm: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
   MIC_CHECK(a->dtype == MIC_BF16 || a->dtype == MIC_F32 || a->dtype == MIC_FP8, "mic_gemm: bad dtype %d", a->dtype);
@@ -113,18 +116,6 @@ static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
   MIC_CHECK(!(a->dact && !a->Zin), "mic_gemm: dact needs Zin");
   MIC_CHECK(a->dropout_p >= 0.f && a->dropout_p < 1.f, "mic_gemm: dropout_p out of range");
   MIC_CHECK(a->c_dtype != MIC_FP8 || a->dtype == MIC_FP8, "mic_gemm: an fp8 C belongs to the fp8 GEMMs");
-  e.C = a->C; e.ldc = a->ldc; e.c_f32 = (a->c_dtype == MIC_F32);
-  e.c_q8 = a->c_dtype == MIC_FP8 ? 1 + a->c_q8_fmt : 0; e.q8_state = a->c_q8_state; e.q8_amax = a->c_q8_amax;
-  e.bias = a->bias; e.act = a->act; e.Zout = a->Zout; e.ldz = a->ldz; e.Zin = a->Zin; e.dact = a->dact;
-  // 16-B vector epilogue: leading dimensions multiples of 8 and every touched base address aligned (an fp8 C is written 8 bytes at
-  // a time); anything else takes the elementwise path
-  e.vec = a->ldc % 8 == 0 && (!(a->Zout || a->Zin) || a->ldz % 8 == 0) && (!a->R || a->ldr % 8 == 0) &&
-          (((uintptr_t)a->Zout | (uintptr_t)a->Zin | (uintptr_t)a->R) & 15) == 0 && ((uintptr_t)a->C & (a->c_dtype == MIC_FP8 ? 7 : 15)) == 0;
-  e.R = a->R; e.ldr = a->ldr; e.accumulate = a->accumulate;
-  e.drop_thr = a->dropout_p > 0.f ? (uint32_t)fminf(a->dropout_p * 4294967296.0f, 4294967295.0f) : 0u;
-  e.drop_seed = a->dropout_seed; e.drop_scale = 1.0f / (1.0f - a->dropout_p);
-  e.alpha = a->alpha == 0.f ? 1.0f : a->alpha; e.N = a->N;
-  e.rowstat = a->rowstat; e.stat_ld = a->rowstat_ld; e.stat_nvalid = a->rowstat_nvalid > 0 ? a->rowstat_nvalid : a->N;
   if (a->rowstat) {
     MIC_CHECK((a->dtype == MIC_BF16 || (a->dtype == MIC_FP8 && !a->a_kmajor)) && a->c_dtype == MIC_BF16 && a->split_k <= 1 && !a->act && !a->dact && !a->R &&
                   !a->accumulate && a->dropout_p == 0.f && !a->Zout,
@@ -132,8 +123,6 @@ static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
     MIC_CHECK(a->N % 64 == 0 && a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0, "mic_gemm: rowstat needs N %% 64 == 0 and a 16-B aligned C");
     MIC_CHECK(a->rowstat_ld >= a->N / 64 && ((uintptr_t)a->rowstat & 7) == 0, "mic_gemm: rowstat needs ld >= N / 64 float2 entries per row");
   }
-  e.ln_stats = a->a_ln_stats; e.ln_g = a->a_ln_colsum; e.ln_bias = nullptr; e.ln_inv_d = 0.f; e.ln_eps = a->a_ln_eps;
-  e.rowsum2 = a->rowsum2;
   if (a->a_ln_stats) {
     MIC_CHECK(a->dtype == MIC_BF16 && a->a_ln_colsum && a->bias && a->a_ln_width > 0, "mic_gemm: a folded LayerNorm needs bf16 operands, a_ln_colsum, bias' and a_ln_width");
     MIC_CHECK(a->split_k <= 1 && !a->dact && !a->accumulate && (a->alpha == 0.f || a->alpha == 1.f), "mic_gemm: folded LayerNorm: no split-K / dact / accumulate / alpha");
@@ -141,7 +130,6 @@ static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
     MIC_CHECK(a->N % 8 == 0 && a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0 && (!a->R || a->ldr % 8 == 0) && (!a->Zout || a->ldz % 8 == 0) &&
                   (((uintptr_t)a->R | (uintptr_t)a->Zout) & 15) == 0,
               "mic_gemm: folded LayerNorm needs the vector epilogue (N, ldc, ldr, ldz multiples of 8, 16-B aligned C / R / Zout)");
-    e.ln_bias = a->bias; e.bias = nullptr; e.ln_inv_d = 1.0f / (float)a->a_ln_width;
   }
   if (a->rowsum2) {
     MIC_CHECK(a->dtype == MIC_BF16 && a->N % 128 == 0 && a->split_k <= 1 && !a->act && !a->dact && !a->Zout && !a->accumulate,
@@ -161,8 +149,27 @@ static int fill_epi(const mic_gemm_args* a, EpiArgs& e) {
   }
   return MIC_OK;
 }
+// the epilogue of one problem as the kernels read it: no checks, no pointer is dereferenced (mic_gemm_plan fills it from argument
+// sets that check_epi would refuse)
+static void fill_epi(const mic_gemm_args* a, EpiArgs& e) {
+  e.C = a->C; e.ldc = a->ldc; e.c_f32 = (a->c_dtype == MIC_F32);
+  e.c_q8 = a->c_dtype == MIC_FP8 ? 1 + a->c_q8_fmt : 0; e.q8_state = a->c_q8_state; e.q8_amax = a->c_q8_amax;
+  e.bias = a->bias; e.act = a->act; e.Zout = a->Zout; e.ldz = a->ldz; e.Zin = a->Zin; e.dact = a->dact;
+  // 16-B vector epilogue: leading dimensions multiples of 8 and every touched base address aligned (an fp8 C is written 8 bytes at
+  // a time); anything else takes the elementwise path
+  e.vec = a->ldc % 8 == 0 && (!(a->Zout || a->Zin) || a->ldz % 8 == 0) && (!a->R || a->ldr % 8 == 0) &&
+          (((uintptr_t)a->Zout | (uintptr_t)a->Zin | (uintptr_t)a->R) & 15) == 0 && ((uintptr_t)a->C & (a->c_dtype == MIC_FP8 ? 7 : 15)) == 0;
+  e.R = a->R; e.ldr = a->ldr; e.accumulate = a->accumulate;
+  e.drop_thr = a->dropout_p > 0.f ? (uint32_t)fminf(a->dropout_p * 4294967296.0f, 4294967295.0f) : 0u;
+  e.drop_seed = a->dropout_seed; e.drop_scale = 1.0f / (1.0f - a->dropout_p);
+  e.alpha = a->alpha == 0.f ? 1.0f : a->alpha; e.N = a->N;
+  e.rowstat = a->rowstat; e.stat_ld = a->rowstat_ld; e.stat_nvalid = a->rowstat_nvalid > 0 ? a->rowstat_nvalid : a->N;
+  e.ln_stats = a->a_ln_stats; e.ln_g = a->a_ln_colsum; e.ln_bias = nullptr; e.ln_inv_d = 0.f; e.ln_eps = a->a_ln_eps;
+  e.rowsum2 = a->rowsum2;
+  if (a->a_ln_stats) { e.ln_bias = a->bias; e.bias = nullptr; e.ln_inv_d = 1.0f / (float)a->a_ln_width; }
+}
 
-bool table_is_plain(const LaunchTable& t) {
+static bool table_is_plain(const LaunchTable& t) {
   for (int i = 0; i < t.count; ++i) {
     const EpiArgs& e = t.p[i].epi;
     if (t.p[i].nsplit > 1 || e.act || e.Zout || e.dact || e.accumulate || (e.ldc & 7)) return false;
@@ -171,22 +178,46 @@ bool table_is_plain(const LaunchTable& t) {
   }
   return true;
 }
-static bool any_rowsum_early(const mic_gemm_args* args, int count) {
-  for (int i = 0; i < count; ++i)
-    if (args[i].a_rowsum) return true;
-  return false;
+
+// ---- the A/B switches of the GEMMs (include/mic_hip.h, tools/README.md): read from the environment once, at the first GEMM /
+// plan / budget call of the process, and latched.  The defaults are the measured best (the measurements stand with the rules
+// in `decide`); nothing on the product path sets them.
+struct GemmSwitches {
+  int free_cus;    // MIC_FREE_CUS: default CU budget (0 = the device's 256)
+  int tile;        // MIC_GEMM_TILE=256|128|64 forces a tile configuration (benchmarking)
+  int tiny_below;  // MIC_TINY_BELOW: 128x128-tile count under which a launch uses 64x64 tiles
+  int quant;       // MIC_GEMM_QUANT=1: the tile-queue comparison of 256^2 against 128^2 also at the full CU budget
+  int t192;        // MIC_GEMM_T192=0: no 192 x 128 tiles
+  int phased;      // MIC_GEMM_PHASED=0: no LDS-DMA four-phase kernel
+  int w4;          // MIC_GEMM_W4=0: no four-wave kernel (gemm_w4.hip)
+  int d2;          // MIC_GEMM_D2: 0 = off; 1 = everything the four-wave kernel would take; 2 = every single-problem NT 256-tile
+                   // launch its epilogue covers; 3 (default) = the launches with softmax partials
+  int kg;          // MIC_GEMM_KG=1|2|4 forces the K-groups of the 64x64 tiles
+  int kg128;       // MIC_GEMM_KG128=1|2 forces the K-groups of the 128x128 tiles
+  int persist;     // MIC_GEMM_PERSIST=0: no persistent grids
+};
+static const GemmSwitches& gemm_switches() {
+  static const GemmSwitches sw = [] {
+    auto env = [](const char* e, int dflt) { return e ? atoi(e) : dflt; };
+    return GemmSwitches{env(getenv("MIC_FREE_CUS"), 0), env(getenv("MIC_GEMM_TILE"), 0), env(getenv("MIC_TINY_BELOW"), MIC_TINY_BELOW),
+                        env(getenv("MIC_GEMM_QUANT"), 0), env(getenv("MIC_GEMM_T192"), 1), env(getenv("MIC_GEMM_PHASED"), 2),
+                        env(getenv("MIC_GEMM_W4"), 1), env(getenv("MIC_GEMM_D2"), 3), env(getenv("MIC_GEMM_KG"), 0),
+                        env(getenv("MIC_GEMM_KG128"), -1), env(getenv("MIC_GEMM_PERSIST"), 1)};
+  }();
+  return sw;
 }
+
 // ---- the CU budget of the tile planner.  Every threshold below that used to say "256" means "the CUs this process's GEMM blocks
 // can expect to get": a launch is "one round" when its blocks fit the budget at the configuration's residency.  Default = the
 // device (256 on MI355X); a data-parallel job whose collectives occupy CUs (RCCL's channels are persistent blocks, one CU each)
 // lowers it — `mic_set_cu_budget`, or MIC_FREE_CUS in the environment — so that a launch sized for 256 free CUs re-plans
 // (fewer K-groups, i.e. more blocks per CU) instead of spilling a few blocks into a second round.
 static thread_local int g_cu_budget = 0;  // per calling thread: two host threads driving two streams plan independently
-int mic_cu_budget_now() {
-  static const int env = [] { const char* e = getenv("MIC_FREE_CUS"); return e ? atoi(e) : 0; }();
+static int mic_cu_budget_now() {
+  const int env = gemm_switches().free_cus;
   int c = g_cu_budget > 0 ? g_cu_budget : (env > 0 ? env : 256);
   c = c < 8 ? 8 : (c > 256 ? 256 : c);
-  return c & ~7;  // whole CUs per XCD: persistent grids are multiples of 8
+  return c & ~7;  // whole CUs per XCD: persistent grids are multiples of 8 (the XCD remap of a persistent grid needs that)
 }
 extern "C" int mic_set_cu_budget(int cus) {
   MIC_CHECK(cus == 0 || (cus >= 8 && cus <= 1024), "mic_set_cu_budget: %d (0 = default, else 8..1024)", cus);
@@ -195,129 +226,15 @@ extern "C" int mic_set_cu_budget(int cus) {
 }
 extern "C" int mic_get_cu_budget(void) { return mic_cu_budget_now(); }
 
-struct GemmPlan { int bm, bm_m, kgroups, blocks, grid, per_cu, phased; };  // bm_m: tile rows (bm, or 192 with bm = 128)
-
-// tile configuration of one (grouped) bf16 / fp8 launch: pure host arithmetic on the shapes and the CU budget
-static GemmPlan plan_bf16(const mic_gemm_args* args, int count) {
-  const int cus = mic_cu_budget_now();
-  GemmPlan pl{};
-  long tiles_big = 0, tiles_small = 0;
-  for (int i = 0; i < count; ++i) {
-    const int sp = args[i].split_k > 1 ? args[i].split_k : 1;
-    tiles_big += (long)((args[i].M + 255) / 256) * ((args[i].N + 255) / 256) * sp;
-    tiles_small += (long)((args[i].M + 127) / 128) * ((args[i].N + 127) / 128) * sp;
-  }
-  // 256x256 tiles deliver 2x the FLOPs per operand byte but need >= ~0.8 blocks per CU to pay; launches that cannot even
-  // give every CU one 128x128 tile (decode-time GEMMs on ~1k rows, the N = 768/1024 projections) run 64x64 tiles, 4 waves,
-  // several blocks per CU.  MIC_GEMM_TILE=256|128|64 forces a configuration (benchmarking).
-  static const int force = [] { const char* e = getenv("MIC_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  static const int tiny_below = [] { const char* e = getenv("MIC_TINY_BELOW"); return e ? atoi(e) : MIC_TINY_BELOW; }();
-  int bm = tiles_big >= (200L * cus) / 256 ? 256 : (tiles_small < ((long)tiny_below * cus) / 256 ? 64 : 128);
-  // ... and a 256x256 launch that fills the CUs 1.1 times costs two rounds.  Under a reduced CU budget (the defaults for all 256
-  // CUs were tuned by measurement and stay as they are; MIC_GEMM_QUANT=1 applies the rule there too) compare the longest per-CU
-  // tile queue of both configurations: a 128x128 tile costs ~0.31 of a 256x256 one in CU time (a quarter of the work at ~0.8 of
-  // the efficiency).
-  static const int quant_env = [] { const char* e = getenv("MIC_GEMM_QUANT"); return e ? atoi(e) : 0; }();
-  if (bm == 256 && (cus < 256 || quant_env)) {
-    const double c256 = (double)((tiles_big + cus - 1) / cus), c128 = 0.3125 * (double)((tiles_small + cus - 1) / cus);
-    if (c128 < c256) bm = 128;
-  }
-  if (force == 256 || force == 128 || force == 64) bm = force;
-  if (args[0].dtype == MIC_FP8 && args[0].a_kmajor && bm < 128) bm = 128;  // fp8 k-major images are 128 wide
-  for (int i = 0; i < count; ++i)
-    if (args[i].c_dtype == MIC_FP8 && bm == 256) bm = 128;  // the fp8-emitting epilogue lives in the 128 / 64 tile kernels
-  for (int i = 0; i < count; ++i)
-    if (args[i].rowstat) bm = 256;  // softmax partials per 64-column granule = the wave tile width of this configuration
-  // 192 x 128 tiles for the single-problem NT / NN launches whose 128 x 128 tiles would need a second round of the 2-per-CU slots
-  // while 192-row tiles fit one (packed decoder rows 2049..3072 and the ViT's 3200 rows against N = 3072 / 4096);
-  // MIC_GEMM_T192=0 switches the configuration off (A/B)
-  static const int t192 = [] { const char* e = getenv("MIC_GEMM_T192"); return e ? atoi(e) : 1; }();
-  int bm_m = bm;
-  // (fp8: measured — the 192-row fp8 tile needs 133 registers, i.e. one block per CU; capped at 128 it spills 59 and the step loses 10 %)
-  if (bm == 128 && t192 && force == 0 && count == 1 && args[0].dtype == MIC_BF16 && !args[0].a_kmajor && args[0].split_k <= 1) {
-    const long t128 = (long)((args[0].M + 127) / 128) * ((args[0].N + 127) / 128), t192n = (long)((args[0].M + 191) / 192) * ((args[0].N + 127) / 128);
-    if (t128 > 2L * cus && t192n <= 2L * cus) bm_m = 192;
-  }
-  int blocks = 0, kmin = 1 << 30;
-  for (int i = 0; i < count; ++i) {
-    int nsplit = args[i].split_k > 1 ? args[i].split_k : 1;
-    const int kt = (args[i].dtype == MIC_FP8 ? args[i].K / 2 : args[i].K) / 64;
-    if (nsplit > kt) nsplit = kt;
-    if (nsplit < 1) nsplit = 1;
-    blocks += ((args[i].M + bm_m - 1) / bm_m) * ((args[i].N + bm - 1) / bm) * nsplit;
-    kmin = kt / nsplit < kmin ? kt / nsplit : kmin;
-  }
-  pl.bm = bm; pl.bm_m = bm_m; pl.blocks = pl.grid = blocks; pl.kgroups = 1; pl.per_cu = 1;
-  // LDS-DMA four-phase 256x256 kernel for the single-problem NT launches (both operands k-contiguous: LM-head forward, FFN-in
-  // forward), where its deeper operand prefetch wins; MIC_GEMM_PHASED=0 switches it off (A/B).  On every 256x256 launch it
-  // measured +1.6 ms per train step (DESIGN.md): that mode is gone.
-  static const int phased_env = [] { const char* e = getenv("MIC_GEMM_PHASED"); return e ? atoi(e) : 2; }();
-  const bool f8 = args[0].dtype == MIC_FP8;
-  pl.phased = bm == 256 && !f8 && phased_env != 0 && !args[0].a_kmajor && !args[0].b_kmajor && count == 1 && !any_rowsum_early(args, count);
-  // ... and of those the four-wave 128x128-wave-tile kernel (gemm_w4.hip) takes, BY DEFAULT, the launches whose shape allows it and
-  // whose epilogue — decided at launch, gemm_w4_takes — is a bare one: bf16 C with bias / folded LayerNorm / softmax partials (LM
-  // head, all-layer cross k/v projection) or fp32 C, also as split-K slabs (the LM head's backward GEMMs on k-contiguous copies);
-  // plan.phased reads 2 for such a shape.  MIC_GEMM_W4=0 keeps them on the four-phase / register-staged kernels (A/B)
-  static const int w4_env = [] { const char* e = getenv("MIC_GEMM_W4"); return e ? atoi(e) : 1; }();
-  if (pl.phased && w4_env && args[0].K >= 256 && args[0].K % 128 == 0) pl.phased = 2;  // (split-K: fp32 slabs, gemm_w4_takes)
-  if (bm == 256) {
-    pl.per_cu = 1;  // 128 KiB of LDS: a block holds its CU alone; PLAIN launches with more tiles than CUs run as `cus` persistent blocks
-  } else if (bm == 128) {
-    // 8 waves (measured better than the 4-wave 64x64 wave tile at every tile count), two blocks per CU; two K-groups (16 waves, one
-    // block per CU) when the launch is a single round of at most one block per CU
-    static const int kg128 = [] { const char* e = getenv("MIC_GEMM_KG128"); return e ? atoi(e) : -1; }();
-    const bool two = bm_m == 128 && (kg128 >= 0 ? kg128 == 2 : (blocks <= cus && kmin >= 8));
-    pl.kgroups = two ? 2 : 1;
-    pl.per_cu = two ? 1 : 2;
-  } else {  // 64x64x64 tiles, 4 waves per K-group (32 KiB of LDS each); K-groups while the grid leaves CUs under-occupied
-    static const int kg_force = [] { const char* e = getenv("MIC_GEMM_KG"); return e ? atoi(e) : 0; }();
-    int kgs = blocks <= cus && kmin >= 16 ? 4 : (blocks <= 2 * cus && kmin >= 8 ? 2 : 1);
-    if (kg_force == 1 || kg_force == 2 || kg_force == 4) kgs = kg_force;
-    pl.kgroups = kgs;
-    pl.per_cu = 4 / kgs;
-  }
-  return pl;
-}
-
-extern "C" int mic_gemm_plan(const mic_gemm_args* args, int count, mic_gemm_plan_info* out) {
-  MIC_CHECK(args && out && count >= 1 && count <= MAX_PROBLEMS, "mic_gemm_plan: bad args (1..%d problems)", MAX_PROBLEMS);
-  MIC_CHECK(args[0].dtype == MIC_BF16 || args[0].dtype == MIC_FP8, "mic_gemm_plan: the planner belongs to the bf16 / fp8 kernels");
-  const GemmPlan pl = plan_bf16(args, count);
-  out->tile = pl.bm; out->tile_m = pl.bm_m; out->kgroups = pl.kgroups; out->blocks = pl.blocks; out->blocks_per_cu = pl.per_cu; out->phased = pl.phased;
-  out->cu_budget = mic_cu_budget_now();
-  // persistent grid: the PLAIN 256x256 instantiations of the register-staged kernel only (launch_cfg_p) — decided from the
-  // epilogue these args describe, and MIC_GEMM_PERSIST
-  static const int persist_env = [] { const char* e = getenv("MIC_GEMM_PERSIST"); return e ? atoi(e) : 1; }();
-  bool plain = true;
-  for (int i = 0; i < count; ++i) {
-    const mic_gemm_args& a = args[i];
-    if (a.split_k > 1 || a.act || a.Zout || a.dact || a.accumulate || (a.ldc & 7) || ((uintptr_t)a.C & 15)) plain = false;
-    if (a.R && ((a.ldr & 7) || ((uintptr_t)a.R & 15) || a.c_dtype == MIC_F32)) plain = false;
-  }
-  const bool persist = persist_env && plain && pl.bm == 256 && !pl.phased && pl.kgroups == 1 && pl.blocks > out->cu_budget;
-  out->grid = persist ? out->cu_budget : pl.blocks;
-  // launches with softmax partials (the LM-head forward) run on gemm_d2.hip by default: 256 x 128 tiles, two blocks per CU
-  static const int d2_plan_env = [] { const char* e = getenv("MIC_GEMM_D2"); return e ? atoi(e) : 3; }();
-  if (d2_plan_env && pl.phased == 2 && count == 1 && args[0].rowstat && args[0].N % 128 == 0) {
-    out->tile = 128; out->tile_m = 256; out->blocks_per_cu = 2;
-    out->blocks = out->grid = ((args[0].M + 255) / 256) * ((args[0].N + 127) / 128);
-  }
-  return MIC_OK;
-}
-
-static int launch_bf16(const mic_gemm_args* args, int count, hipStream_t s) {
-  LaunchTable tab;
+// ---- the launch table of a (grouped) bf16 / fp8 launch apart from its tiling: pure arithmetic on the arguments, no checks, no
+// pointer dereferenced — the launcher runs check_table on it, mic_gemm_plan builds it from argument sets mic_gemm would refuse
+static void fill_table(const mic_gemm_args* args, int count, LaunchTable& tab) {
   tab.count = count;
-  const int f8 = args[0].dtype == MIC_FP8 ? (args[0].a_fmt == MIC_E5M2 ? 2 : 1) : 0;
-  const GemmPlan pl = plan_bf16(args, count);
-  const int bm = pl.bm, bm_m = pl.bm_m;
-  int blocks = 0;
+  tab.total_blocks = 0;
+  const bool f8 = args[0].dtype == MIC_FP8;
   for (int i = 0; i < count; ++i) {
     Problem& p = tab.p[i];
-    if (int rc = fill_epi(&args[i], p.epi)) return rc;
-    MIC_CHECK(args[i].a_kmajor == args[0].a_kmajor && args[i].b_kmajor == args[0].b_kmajor && args[i].dtype == args[0].dtype &&
-                  (args[i].dtype == MIC_BF16 || (args[i].dtype == MIC_FP8 && args[i].a_fmt == args[0].a_fmt)),
-              "mic_gemm_grouped: all problems of a group must share dtype (bf16 / fp8 format) and operand layouts");
+    fill_epi(&args[i], p.epi);
     p.A = (const uint16_t*)args[i].A; p.B = (const uint16_t*)args[i].B;
     p.lda = args[i].lda; p.ldb = args[i].ldb; p.M = args[i].M; p.N = args[i].N; p.K = args[i].K;
     p.sa = p.sb = nullptr;
@@ -326,10 +243,35 @@ static int launch_bf16(const mic_gemm_args* args, int count, hipStream_t s) {
       p.K /= 2;
       p.sa = args[i].a_scale_inv; p.sb = args[i].b_scale_inv;
     }
-    p.tiles_m = (p.M + bm_m - 1) / bm_m; p.tiles_n = (p.N + bm - 1) / bm;
+    p.tiles_m = p.tiles_n = p.block_begin = 0;  // tile_table
     p.nsplit = args[i].split_k > 1 ? args[i].split_k : 1;
     if (p.nsplit > p.K / 64) p.nsplit = p.K / 64;
+    if (p.nsplit < 1) p.nsplit = 1;  // (K < 64: refused at launch, still planned)
     p.split_stride = p.nsplit > 1 ? args[i].split_stride : 0;
+    p.a_rowsum = args[i].a_rowsum;
+    p.rowsum_k = args[i].rowsum_k > 0 ? args[i].rowsum_k : p.K;
+    p.k_valid = args[i].k_valid > 0 ? args[i].k_valid : 0x7fffffff;
+  }
+}
+// the tiling of a filled table: tile_m x tile_n tiles, the problems' blocks one after another
+static void tile_table(LaunchTable& tab, int tile_m, int tile_n) {
+  int blocks = 0;
+  for (int i = 0; i < tab.count; ++i) {
+    Problem& p = tab.p[i];
+    p.tiles_m = (p.M + tile_m - 1) / tile_m; p.tiles_n = (p.N + tile_n - 1) / tile_n;
+    p.block_begin = blocks;
+    blocks += p.tiles_m * p.tiles_n * p.nsplit;
+  }
+  tab.total_blocks = blocks;
+}
+// the host checks of a launch (mic_gemm / mic_gemm_grouped only): every problem's own, then those of the group
+static int check_table(const mic_gemm_args* args, int count, const LaunchTable& tab, bool plain) {
+  for (int i = 0; i < count; ++i) {
+    const Problem& p = tab.p[i];
+    if (int rc = check_epi(&args[i])) return rc;
+    MIC_CHECK(args[i].a_kmajor == args[0].a_kmajor && args[i].b_kmajor == args[0].b_kmajor && args[i].dtype == args[0].dtype &&
+                  (args[i].dtype == MIC_BF16 || (args[i].dtype == MIC_FP8 && args[i].a_fmt == args[0].a_fmt)),
+              "mic_gemm_grouped: all problems of a group must share dtype (bf16 / fp8 format) and operand layouts");
     MIC_CHECK(args[i].split_stride >= 0 && (args[i].split_stride == 0 || args[i].split_stride >= (long long)(p.M - 1) * args[i].ldc + p.N),
               "mic_gemm: split_stride must cover one M x N slab");
     // (tested on the arguments: with split_k clamped to 1 the launch would fill slab 0 alone and leave the others to the caller's sum)
@@ -337,39 +279,136 @@ static int launch_bf16(const mic_gemm_args* args, int count, hipStream_t s) {
     MIC_CHECK(p.split_stride % 4 == 0 && (p.split_stride == 0 || ((uintptr_t)args[i].C & 15) == 0),
               "mic_gemm: a split-K slab workspace is 16-B aligned with split_stride %% 4 == 0 (mic_sum_slabs reads it as 16-B vectors)");
     MIC_CHECK(!args[i].a_rowsum || args[i].a_kmajor, "mic_gemm: a_rowsum needs a_kmajor (A = dy^T of the weight-gradient GEMM)");
-    p.a_rowsum = args[i].a_rowsum;
-    p.rowsum_k = args[i].rowsum_k > 0 ? args[i].rowsum_k : p.K;
     MIC_CHECK(args[i].k_valid >= 0 && (args[i].k_valid == 0 || (args[i].a_kmajor && args[i].b_kmajor)),
               "mic_gemm: k_valid is a feature of the k-major x k-major (weight-gradient) launches");
-    p.k_valid = args[i].k_valid > 0 ? args[i].k_valid : 0x7fffffff;
-    p.block_begin = blocks;
-    blocks += p.tiles_m * p.tiles_n * p.nsplit;
   }
-  tab.total_blocks = blocks;
   for (int i = 0; i < count; ++i) {
-    MIC_CHECK(!args[i].rowsum2 || table_is_plain(tab), "mic_gemm_grouped: rowsum2 needs every problem of the launch on the bare / residual epilogue");
+    MIC_CHECK(!args[i].rowsum2 || plain, "mic_gemm_grouped: rowsum2 needs every problem of the launch on the bare / residual epilogue");
     // (the softmax partials are written by the PLAIN epilogue and by gemm_w4 / gemm_d2, which take single-problem launches only)
-    MIC_CHECK(!args[i].rowstat || table_is_plain(tab), "mic_gemm_grouped: rowstat needs every problem of the launch on the bare / residual epilogue");
+    MIC_CHECK(!args[i].rowstat || plain, "mic_gemm_grouped: rowstat needs every problem of the launch on the bare / residual epilogue");
   }
+  return MIC_OK;
+}
+
+// ---- THE dispatch decision of one (grouped) bf16 / fp8 launch: kernel family, tiling, K-groups, epilogue instantiation and grid
+// — pure host arithmetic on the shapes, the epilogues (`tab`: fill_table), the CU budget and the switches.  launch_bf16 launches
+// what it says and mic_gemm_plan reports what it says; no rule lives anywhere else.  Leaves `tab` tiled for the decision.
+static GemmDecision decide(const mic_gemm_args* args, int count, LaunchTable& tab) {
+  const GemmSwitches& sw = gemm_switches();
+  const int cus = mic_cu_budget_now();
+  GemmDecision d{};
+  d.akm = args[0].a_kmajor != 0; d.bkm = args[0].b_kmajor != 0;
+  d.f8 = args[0].dtype == MIC_FP8 ? (args[0].a_fmt == MIC_E5M2 ? 2 : 1) : 0;
+  d.plain = table_is_plain(tab);
+  long tiles_big = 0, tiles_small = 0;
+  bool rowstat = false, rowsum = false, c_q8 = false;
+  for (int i = 0; i < count; ++i) {
+    const int sp = args[i].split_k > 1 ? args[i].split_k : 1;
+    tiles_big += (long)((args[i].M + 255) / 256) * ((args[i].N + 255) / 256) * sp;
+    tiles_small += (long)((args[i].M + 127) / 128) * ((args[i].N + 127) / 128) * sp;
+    rowstat |= args[i].rowstat != nullptr; rowsum |= args[i].a_rowsum != nullptr; c_q8 |= args[i].c_dtype == MIC_FP8;
+  }
+  // 256x256 tiles deliver 2x the FLOPs per operand byte but need >= ~0.8 blocks per CU to pay; launches that cannot even
+  // give every CU one 128x128 tile (decode-time GEMMs on ~1k rows, the N = 768/1024 projections) run 64x64 tiles, 4 waves,
+  // several blocks per CU.  MIC_GEMM_TILE=256|128|64 forces a configuration (benchmarking).
+  int bm = tiles_big >= (200L * cus) / 256 ? 256 : (tiles_small < ((long)sw.tiny_below * cus) / 256 ? 64 : 128);
+  // ... and a 256x256 launch that fills the CUs 1.1 times costs two rounds.  Under a reduced CU budget (the defaults for all 256
+  // CUs were tuned by measurement and stay as they are; MIC_GEMM_QUANT=1 applies the rule there too) compare the longest per-CU
+  // tile queue of both configurations: a 128x128 tile costs ~0.31 of a 256x256 one in CU time (a quarter of the work at ~0.8 of
+  // the efficiency).
+  if (bm == 256 && (cus < 256 || sw.quant)) {
+    const double c256 = (double)((tiles_big + cus - 1) / cus), c128 = 0.3125 * (double)((tiles_small + cus - 1) / cus);
+    if (c128 < c256) bm = 128;
+  }
+  const int force = sw.tile == 256 || sw.tile == 128 || sw.tile == 64 ? sw.tile : 0;
+  if (force) bm = force;
+  if (d.f8 && d.akm && bm < 128) bm = 128;  // fp8 k-major images are 128 wide
+  if (c_q8 && bm == 256) bm = 128;          // the fp8-emitting epilogue lives in the 128 / 64 tile kernels
+  if (rowstat) bm = 256;                    // softmax partials per 64-column granule = the wave tile width of this configuration
+  // 192 x 128 tiles for the single-problem NT / NN launches whose 128 x 128 tiles would need a second round of the 2-per-CU slots
+  // while 192-row tiles fit one (packed decoder rows 2049..3072 and the ViT's 3200 rows against N = 3072 / 4096);
+  // MIC_GEMM_T192=0 switches the configuration off (A/B)
+  // (fp8: measured — the 192-row fp8 tile needs 133 registers, i.e. one block per CU; capped at 128 it spills 59 and the step loses 10 %)
+  bool t192 = false;
+  if (bm == 128 && sw.t192 && sw.tile == 0 && count == 1 && !d.f8 && !d.akm && args[0].split_k <= 1) {
+    const long t128 = (long)((args[0].M + 127) / 128) * ((args[0].N + 127) / 128), t192n = (long)((args[0].M + 191) / 192) * ((args[0].N + 127) / 128);
+    t192 = t128 > 2L * cus && t192n <= 2L * cus;
+  }
+  // LDS-DMA four-phase 256x256 kernel for the single-problem NT launches (both operands k-contiguous: LM-head forward, FFN-in
+  // forward), where its deeper operand prefetch wins; MIC_GEMM_PHASED=0 switches it off (A/B).  On every 256x256 launch it
+  // measured +1.6 ms per train step (DESIGN.md): that mode is gone.
+  const bool nt1 = bm == 256 && !d.f8 && !d.akm && !d.bkm && count == 1;
+  d.phased = nt1 && sw.phased != 0 && !rowsum;
+  // ... and of those the four-wave 128x128-wave-tile kernel (gemm_w4.hip) takes, BY DEFAULT, the launches whose shape allows it and
+  // whose epilogue (gemm_w4_takes) is a bare one: bf16 C with bias / folded LayerNorm / softmax partials (LM head, all-layer cross
+  // k/v projection) or fp32 C, also as split-K slabs (the LM head's backward GEMMs on k-contiguous copies); the legacy report field
+  // `phased` reads 2 for such a SHAPE whatever the epilogue.  MIC_GEMM_W4=0 keeps them on the four-phase / register-staged kernels (A/B)
+  if (d.phased && sw.w4 && args[0].K >= 256 && args[0].K % 128 == 0) d.phased = 2;
+  const int w4_epi = d.phased == 2 ? gemm_w4_takes(tab) : -1;
   // The two-blocks-per-CU 256 x 128 kernel (gemm_d2.hip) takes the four-wave kernel's launches that carry softmax partials (the
   // LM-head forward: K = 1024 tiles whose epilogue is a third of their time — under a second block's MFMAs it is cover).  Its K loop
   // is slower than the four-wave kernel's (64-B DMA segments: bound by L2 requests), so the deep-K and bare launches stay there.
-  // MIC_GEMM_D2 (A/B): 0 = off; 1 = everything the four-wave kernel would take; 2 = every single-problem NT 256-tile launch its
-  // epilogue covers; 3 (default) = the launches with softmax partials
-  static const int d2_env = [] { const char* e = getenv("MIC_GEMM_D2"); return e ? atoi(e) : 3; }();
-  const bool nt1 = bm == 256 && !f8 && !args[0].a_kmajor && !args[0].b_kmajor && count == 1;
-  if (d2_env && nt1 && gemm_d2_takes(tab) && (d2_env == 2 || (pl.phased == 2 && gemm_w4_takes(tab))) && (d2_env != 3 || tab.p[0].epi.rowstat)) {
-    Problem& p = tab.p[0];
-    p.tiles_n = (p.N + 127) / 128;  // 256 x 128 tiles
-    tab.total_blocks = p.tiles_m * p.tiles_n * p.nsplit;
-    launch_gemm_d2(tab, s);
-  } else
-  if (bm == 256 && pl.phased == 2 && gemm_w4_takes(tab)) launch_gemm_w4(tab, s);  // 4 waves x 128x128, bare epilogues (default on)
-  else if (bm == 256 && pl.phased && tab.p[0].nsplit == 1) launch_gemm_phased(tab, args[0].a_kmajor, args[0].b_kmajor, table_is_plain(tab), s);  // LDS-DMA, phased
-  else if (bm == 256) launch_gemm_t256(tab, args[0].a_kmajor, args[0].b_kmajor, s, f8);     // 256x256x64, 8 waves
-  else if (bm == 128 && bm_m == 192) launch_gemm_t192(tab, args[0].b_kmajor, s);                     // 192x128x64, 8 waves, two blocks per CU
-  else if (bm == 128) launch_gemm_t128(tab, args[0].a_kmajor, args[0].b_kmajor, s, f8, pl.kgroups);  // 128x128x64, 8 waves per K-group
-  else launch_gemm_t64(tab, args[0].a_kmajor, args[0].b_kmajor, s, f8, pl.kgroups);                  // 64x64x64, 4 waves per K-group
+  // MIC_GEMM_D2 (A/B): see GemmSwitches
+  const int d2_epi = sw.d2 && nt1 ? gemm_d2_takes(tab) : -1;
+  if (d2_epi >= 0 && (sw.d2 == 2 || w4_epi >= 0) && (sw.d2 != 3 || tab.p[0].epi.rowstat)) d.family = GEMM_D2;
+  else if (w4_epi >= 0) d.family = GEMM_W4;                                  // 4 waves x 128x128, bare epilogues
+  else if (bm == 256 && d.phased && tab.p[0].nsplit == 1) d.family = GEMM_PHASED;  // LDS-DMA, four-phase schedule
+  else d.family = bm == 256 ? GEMM_T256 : (t192 ? GEMM_T192 : (bm == 128 ? GEMM_T128 : GEMM_T64));
+  d.tile_m = d.family == GEMM_T192 ? 192 : bm;
+  d.tile_n = d.family == GEMM_D2 ? 128 : bm;
+  d.epi = d.family == GEMM_D2 ? d2_epi : (d.family == GEMM_W4 ? w4_epi : 0);
+  tile_table(tab, d.tile_m, d.tile_n);
+  d.blocks = d.grid = tab.total_blocks;
+  int kmin = 1 << 30;  // the shortest K range of a block, in 64-k (fp8: 128-k) tiles
+  for (int i = 0; i < count; ++i) kmin = tab.p[i].K / 64 / tab.p[i].nsplit < kmin ? tab.p[i].K / 64 / tab.p[i].nsplit : kmin;
+  d.kgroups = 1;
+  d.per_cu = 1;  // 256 x 256 tiles, 128 KiB of LDS: a block holds its CU alone
+  if (d.family == GEMM_D2 || d.family == GEMM_T192) {
+    d.per_cu = 2;
+  } else if (d.family == GEMM_T256) {
+    // PLAIN launches with more tiles than (free) CUs run as that many persistent blocks (the PLAIN 256x256 instantiations of
+    // gemm_kernel.h walk the tiles bid, bid + grid, ...); MIC_GEMM_PERSIST=0 switches that off (A/B)
+    if (sw.persist && d.plain && d.blocks > cus) d.grid = cus;
+  } else if (d.family == GEMM_T128) {
+    // 8 waves (measured better than the 4-wave 64x64 wave tile at every tile count), two blocks per CU; two K-groups (16 waves, one
+    // block per CU) when the launch is a single round of at most one block per CU
+    const bool two = sw.kg128 >= 0 ? sw.kg128 == 2 : (d.blocks <= cus && kmin >= 8);
+    d.kgroups = two ? 2 : 1;
+    d.per_cu = two ? 1 : 2;
+  } else if (d.family == GEMM_T64) {  // 64x64x64 tiles, 4 waves per K-group (32 KiB of LDS each); K-groups while the grid leaves CUs under-occupied
+    d.kgroups = d.blocks <= cus && kmin >= 16 ? 4 : (d.blocks <= 2 * cus && kmin >= 8 ? 2 : 1);
+    if (sw.kg == 1 || sw.kg == 2 || sw.kg == 4) d.kgroups = sw.kg;
+    d.per_cu = 4 / d.kgroups;
+  }
+  return d;
+}
+
+extern "C" int mic_gemm_plan(const mic_gemm_args* args, int count, mic_gemm_plan_info* out) {
+  MIC_CHECK(args && out && count >= 1 && count <= MAX_PROBLEMS, "mic_gemm_plan: bad args (1..%d problems)", MAX_PROBLEMS);
+  MIC_CHECK(args[0].dtype == MIC_BF16 || args[0].dtype == MIC_FP8, "mic_gemm_plan: the planner belongs to the bf16 / fp8 kernels");
+  LaunchTable tab;
+  fill_table(args, count, tab);
+  const GemmDecision d = decide(args, count, tab);
+  out->tile = d.tile_n; out->tile_m = d.tile_m; out->kgroups = d.kgroups; out->blocks = d.blocks; out->grid = d.grid;
+  out->blocks_per_cu = d.per_cu; out->phased = d.phased; out->cu_budget = mic_cu_budget_now();
+  out->family = d.family; out->plain = d.plain; out->epi = d.epi;
+  return MIC_OK;
+}
+
+static int launch_bf16(const mic_gemm_args* args, int count, hipStream_t s) {
+  LaunchTable tab;
+  fill_table(args, count, tab);
+  const GemmDecision d = decide(args, count, tab);
+  if (int rc = check_table(args, count, tab, d.plain)) return rc;
+  switch (d.family) {
+    case GEMM_D2: launch_gemm_d2(tab, d, s); break;          // 256x128, 4 waves, two blocks per CU
+    case GEMM_W4: launch_gemm_w4(tab, d, s); break;          // 256x256, 4 waves x 128x128
+    case GEMM_PHASED: launch_gemm_phased(tab, d, s); break;  // 256x256, 8 waves, LDS-DMA, phased
+    case GEMM_T256: launch_gemm_t256(tab, d, s); break;      // 256x256x64, 8 waves
+    case GEMM_T192: launch_gemm_t192(tab, d, s); break;      // 192x128x64, 8 waves, two blocks per CU
+    case GEMM_T128: launch_gemm_t128(tab, d, s); break;      // 128x128x64, 8 waves per K-group
+    default: launch_gemm_t64(tab, d, s); break;              // 64x64x64, 4 waves per K-group
+  }
   MIC_LAUNCH_CHECK();
   return MIC_OK;
 }
@@ -379,7 +418,8 @@ extern "C" int mic_gemm(const mic_gemm_args* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (a->dtype == MIC_BF16 || a->dtype == MIC_FP8) return launch_bf16(a, 1, s);
   EpiArgs e;
-  if (int rc = fill_epi(a, e)) return rc;
+  if (int rc = check_epi(a)) return rc;
+  fill_epi(a, e);
   MIC_CHECK(a->split_k <= 1, "mic_gemm(f32): split_k is a bf16-path feature");
   MIC_CHECK(!a->a_rowsum, "mic_gemm(f32): a_rowsum is a bf16-path feature (use mic_colsum)");
   MIC_CHECK(a->k_valid == 0, "mic_gemm(f32): k_valid is a bf16-path feature");

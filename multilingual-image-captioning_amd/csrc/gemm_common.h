@@ -20,22 +20,33 @@ struct Problem {
   EpiArgs epi;
 };
 struct LaunchTable { int count; int total_blocks; Problem p[MAX_PROBLEMS]; };
-// CUs the planner sizes one-round launches and persistent grids for (gemm.hip: mic_set_cu_budget / MIC_FREE_CUS; multiple of 8)
-int mic_cu_budget_now();
+// What one launch runs (gemm.hip: `decide`, the only place that chooses; mic_gemm_plan reports the same struct).  The launchers
+// below decide nothing: they pick the instantiation the decision names and launch `grid` blocks on a table tiled for it.
+enum GemmFamily { GEMM_T64 = 0, GEMM_T128, GEMM_T192, GEMM_T256, GEMM_PHASED, GEMM_W4, GEMM_D2 };  // (numbering: mic_gemm_plan_info.family)
+struct GemmDecision {
+  int family;          // GemmFamily
+  int tile_m, tile_n;  // tile rows x columns
+  int kgroups, per_cu; // K-groups per block; blocks of this configuration that fit one CU
+  int akm, bkm, f8;    // operand layouts; 0 = bf16, 1 = e4m3 x e4m3, 2 = e5m2 x e4m3
+  int plain;           // every problem on the bare / residual epilogue: the PLAIN instantiations (gemm_kernel.h)
+  int epi;             // gemm_w4_kernel<epi> / gemm_d2_kernel<epi>; 0 for the other families
+  int blocks, grid;    // logical blocks; launched grid (persistent 256x256 launches: the CU budget, a multiple of 8)
+  int phased;          // legacy report field (mic_gemm_plan_info.phased): 0, 1 = the shape fits the four-phase kernel, 2 = ... the four-wave one
+};
 // gemm_phased.hip: 256x256 tiles, LDS-DMA operands, four-phase K-tile schedule (bf16 operands, no K-groups)
-void launch_gemm_phased(const LaunchTable& tab, int akm, int bkm, bool plain, hipStream_t s);
-// gemm_w4.hip: 256x256 tiles on four waves (128x128 wave tiles, one wave per SIMD), LDS-DMA ring of 32-k steps; NT, single problem
-bool gemm_w4_takes(const LaunchTable& tab);
-void launch_gemm_w4(const LaunchTable& tab, hipStream_t s);
+void launch_gemm_phased(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
+// gemm_w4.hip: 256x256 tiles on four waves (128x128 wave tiles, one wave per SIMD), LDS-DMA ring of 32-k steps; NT, single problem.
+// *_takes (called by `decide` alone, for bf16 NT launches): the epilogue instantiation that takes the launch, or -1
+int gemm_w4_takes(const LaunchTable& tab);
+void launch_gemm_w4(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
 // gemm_d2.hip: 256x128 tiles on four waves (128x64 wave tiles), two blocks per CU, LDS-DMA ring of 32-k steps; NT, single problem
-bool gemm_d2_takes(const LaunchTable& tab);
-void launch_gemm_d2(const LaunchTable& tab, hipStream_t s);
+int gemm_d2_takes(const LaunchTable& tab);
+void launch_gemm_d2(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
 // one translation unit per tile configuration of the main kernel (gemm_kernel.h): 256x256 / 128x128 (K-groups 1, 2) / 64x64 (1, 2, 4)
-bool table_is_plain(const LaunchTable& t);
-void launch_gemm_t256(const LaunchTable& tab, int akm, int bkm, hipStream_t s, int f8);
-void launch_gemm_t128(const LaunchTable& tab, int akm, int bkm, hipStream_t s, int f8, int kgroups);
-void launch_gemm_t192(const LaunchTable& tab, int bkm, hipStream_t s);  // 192 x 128 tiles, bf16, k-contiguous A (NT / NN)
-void launch_gemm_t64(const LaunchTable& tab, int akm, int bkm, hipStream_t s, int f8, int kgroups);
+void launch_gemm_t256(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
+void launch_gemm_t128(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
+void launch_gemm_t192(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);  // 192 x 128 tiles, bf16, k-contiguous A (NT / NN)
+void launch_gemm_t64(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
 
 // --- stage one operand image (ROWS x BKT k, or BKT k x ROWS x; ROWS = 128 or 64) HBM/L2 -> registers -> LDS.
 //     Measured on gfx950: a global_load_lds (LDS-DMA) instruction costs ~100 cycles of issue time in the issuing wave's

@@ -295,24 +295,25 @@ void launch_d2(const LaunchTable& tab, hipStream_t s) {
 
 // the launches this kernel takes: one problem, NT, K >= 128, whole 8-column units with 16-B aligned rows everywhere; no folded
 // LayerNorm / rowsum2 by-products (they stay with the other kernels); split-K as fp32 slabs
-bool gemm_d2_takes(const LaunchTable& tab) {
-  if (tab.count != 1) return false;
+// -> the epilogue instantiation (1 = with softmax partials, 0 = without), or -1: not this kernel's launch
+int gemm_d2_takes(const LaunchTable& tab) {
+  if (tab.count != 1) return -1;
   const Problem& p = tab.p[0];
   const EpiArgs& e = p.epi;
   const long long lim = 0x7fffffffLL;  // buffer resources with 32-bit lane offsets (gemm_w4.hip)
-  if ((long long)p.M * p.lda * 2 >= lim || (long long)p.N * p.ldb * 2 >= lim) return false;
-  if (p.K < 128 || p.K % 64 != 0 || p.N % 8 != 0 || e.rowsum2 || e.ln_stats) return false;
-  if (((uintptr_t)e.C & 15) != 0 || (e.ldc & 7) != 0) return false;
-  if ((e.Zout || e.Zin) && ((e.ldz & 7) != 0 || ((uintptr_t)(e.Zout ? e.Zout : e.Zin) & 15) != 0)) return false;
-  if (e.R && ((e.ldr & 7) != 0 || ((uintptr_t)e.R & 15) != 0)) return false;
-  if (e.dact && e.accumulate && !e.c_f32) return false;  // (epilogue_pre_ok)
-  if (!e.vec) return false;  // its side loads are 16-B vectors: every leading dimension and base address aligned (fill_epi)
-  if (p.nsplit > 1 && !(e.c_f32 && p.split_stride > 0)) return false;
-  if (e.rowstat && (e.c_f32 || e.act || e.Zout || e.dact || e.R || e.drop_thr || e.accumulate)) return false;
-  return true;
+  if ((long long)p.M * p.lda * 2 >= lim || (long long)p.N * p.ldb * 2 >= lim) return -1;
+  if (p.K < 128 || p.K % 64 != 0 || p.N % 8 != 0 || e.rowsum2 || e.ln_stats) return -1;
+  if (((uintptr_t)e.C & 15) != 0 || (e.ldc & 7) != 0) return -1;
+  if ((e.Zout || e.Zin) && ((e.ldz & 7) != 0 || ((uintptr_t)(e.Zout ? e.Zout : e.Zin) & 15) != 0)) return -1;
+  if (e.R && ((e.ldr & 7) != 0 || ((uintptr_t)e.R & 15) != 0)) return -1;
+  if (e.dact && e.accumulate && !e.c_f32) return -1;  // (epilogue_pre_ok)
+  if (!e.vec) return -1;  // its side loads are 16-B vectors: every leading dimension and base address aligned (fill_epi)
+  if (p.nsplit > 1 && !(e.c_f32 && p.split_stride > 0)) return -1;
+  if (e.rowstat && (e.c_f32 || e.act || e.Zout || e.dact || e.R || e.drop_thr || e.accumulate)) return -1;
+  return e.rowstat ? 1 : 0;
 }
-void launch_gemm_d2(const LaunchTable& tab, hipStream_t s) {
-  if (tab.p[0].epi.rowstat) launch_d2<1>(tab, s);
+void launch_gemm_d2(const LaunchTable& tab, const GemmDecision& d, hipStream_t s) {
+  if (d.epi == 1) launch_d2<1>(tab, s);
   else launch_d2<0>(tab, s);
 }
 

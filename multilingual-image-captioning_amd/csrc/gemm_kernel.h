@@ -319,19 +319,16 @@ __global__ __launch_bounds__(128 * WNW * KG, KG > 1 ? 1 : 2) void gemm_bf16_kern
 }
 
 template <int WM, int WN, int WNW, int BKT, int KG, bool PLAIN, int F8 = 0>
-static inline void launch_cfg_p(const LaunchTable& tab, int akm, int bkm, hipStream_t s) {
+static inline void launch_cfg_p(const LaunchTable& tab, const GemmDecision& d, hipStream_t s) {
   constexpr int BM = 2 * WM, BN = WN * WNW;
   size_t lds = (size_t)KG * 2 * (BM + BN) * BKT * 2;
   const size_t epi = (size_t)2 * WNW * (WM % 64 == 0 ? 64 : 32) * WN * 4;  // the epilogue restages 64 (or 32) x WN floats per wave
   const size_t red = (size_t)(KG - 1) * 2 * WNW * (WM / 32) * (WN / 32) * 16 * 64 * 4;  // K-group partial sums
   if (epi > lds) lds = epi;
   if (red > lds) lds = red;
-  // 256x256 tiles hold a CU alone (128 KiB LDS): launches with more tiles than (free) CUs run as that many persistent blocks
-  static const int persist = [] { const char* e = getenv("MIC_GEMM_PERSIST"); return e ? atoi(e) : 1; }();
-  int nblk = tab.total_blocks;
-  const int cus = mic_cu_budget_now();  // a multiple of 8 (the XCD remap of a persistent grid needs that)
-  if (persist && BM == 256 && PLAIN && KG == 1 && nblk > cus) nblk = cus;
-  dim3 grid(nblk), block(128 * WNW * KG);
+  // (d.grid < tab.total_blocks: a persistent launch — `decide` grants that to the PLAIN 256x256 instantiations alone)
+  const int akm = d.akm, bkm = d.bkm;
+  dim3 grid(d.grid), block(128 * WNW * KG);
 #define LAUNCH(AKM, BKMM)                                                                                                  \
   do {                                                                                                                     \
     static bool attr_set_dev[64] = {}; /* per instantiation AND device (the attribute belongs to the device's code object) */ \
@@ -365,15 +362,14 @@ static inline void launch_cfg_p(const LaunchTable& tab, int akm, int bkm, hipStr
 }
 
 template <int WM, int WN, int WNW, int BKT, int KG = 1>
-static inline void launch_cfg(const LaunchTable& tab, int akm, int bkm, hipStream_t s, int f8 = 0) {
-  const bool plain = table_is_plain(tab);
-  if (f8 == 1) {
-    if (plain) launch_cfg_p<WM, WN, WNW, BKT, KG, true, 1>(tab, akm, bkm, s);
-    else launch_cfg_p<WM, WN, WNW, BKT, KG, false, 1>(tab, akm, bkm, s);
-  } else if (f8 == 2) {
-    if (plain) launch_cfg_p<WM, WN, WNW, BKT, KG, true, 2>(tab, akm, bkm, s);
-    else launch_cfg_p<WM, WN, WNW, BKT, KG, false, 2>(tab, akm, bkm, s);
-  } else if (plain) launch_cfg_p<WM, WN, WNW, BKT, KG, true>(tab, akm, bkm, s);
-  else launch_cfg_p<WM, WN, WNW, BKT, KG, false>(tab, akm, bkm, s);
+static inline void launch_cfg(const LaunchTable& tab, const GemmDecision& d, hipStream_t s) {
+  if (d.f8 == 1) {
+    if (d.plain) launch_cfg_p<WM, WN, WNW, BKT, KG, true, 1>(tab, d, s);
+    else launch_cfg_p<WM, WN, WNW, BKT, KG, false, 1>(tab, d, s);
+  } else if (d.f8 == 2) {
+    if (d.plain) launch_cfg_p<WM, WN, WNW, BKT, KG, true, 2>(tab, d, s);
+    else launch_cfg_p<WM, WN, WNW, BKT, KG, false, 2>(tab, d, s);
+  } else if (d.plain) launch_cfg_p<WM, WN, WNW, BKT, KG, true>(tab, d, s);
+  else launch_cfg_p<WM, WN, WNW, BKT, KG, false>(tab, d, s);
 }
 

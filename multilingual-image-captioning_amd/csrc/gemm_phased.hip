@@ -259,8 +259,8 @@ void launch_one(const LaunchTable& tab, hipStream_t s) {
 
 // NT launches only (both operands k-contiguous): the dispatcher takes this kernel for the single-problem NT 256x256 launches, where
 // it measured faster than the register-staged kernel; on the k-major layouts it lost, those instantiations are not built.
-void launch_gemm_phased(const LaunchTable& tab, int akm, int bkm, bool plain, hipStream_t s) {
-  if (akm || bkm) { mic_set_error("launch_gemm_phased: NT launches only"); return; }
-  if (plain) launch_one<false, false, true>(tab, s);
+void launch_gemm_phased(const LaunchTable& tab, const GemmDecision& d, hipStream_t s) {
+  if (d.akm || d.bkm) { mic_set_error("launch_gemm_phased: NT launches only"); return; }
+  if (d.plain) launch_one<false, false, true>(tab, s);
   else launch_one<false, false, false>(tab, s);
 }

@@ -369,26 +369,26 @@ void launch_w4(const LaunchTable& tab, hipStream_t s) {
 
 // the launches this kernel takes: one problem, NT, no split, K a multiple of 128 and >= 256, bf16 C through the bare epilogue
 // (alpha, bias, folded LayerNorm, softmax partials — the LM head and the all-layer cross k/v projection)
-bool gemm_w4_takes(const LaunchTable& tab) {
-  if (tab.count != 1) return false;
+// -> the epilogue instantiation (2 bare; + 1 softmax partials; + 4 folded LayerNorm; 8 = fp32 C), or -1: not this kernel's launch
+int gemm_w4_takes(const LaunchTable& tab) {
+  if (tab.count != 1) return -1;
   const Problem& p = tab.p[0];
   const EpiArgs& e = p.epi;
   // the DMA addresses an operand through a buffer resource of 2^31 - 1 bytes with 32-bit lane offsets: larger operands stay on the
   // four-phase kernel (64-bit addresses)
   const long long lim = 0x7fffffffLL;
-  if ((long long)p.M * p.lda * 2 >= lim || (long long)p.N * p.ldb * 2 >= lim) return false;
-  if (p.K < 256 || p.K % 128 != 0 || e.R || e.drop_thr || e.rowsum2 || e.act || e.Zout || e.dact || e.accumulate) return false;
-  if (((uintptr_t)e.C & 15) != 0) return false;
+  if ((long long)p.M * p.lda * 2 >= lim || (long long)p.N * p.ldb * 2 >= lim) return -1;
+  if (p.K < 256 || p.K % 128 != 0 || e.R || e.drop_thr || e.rowsum2 || e.act || e.Zout || e.dact || e.accumulate) return -1;
+  if (((uintptr_t)e.C & 15) != 0) return -1;
   if (e.c_f32)  // fp32 C (one slab per split with split-K): alpha and bias only
-    return !e.rowstat && !e.ln_stats && (p.nsplit == 1 || p.split_stride > 0) && p.K / 64 / p.nsplit >= 2;
+    return !e.rowstat && !e.ln_stats && (p.nsplit == 1 || p.split_stride > 0) && p.K / 64 / p.nsplit >= 2 ? 8 : -1;
   // bf16 C: bias, folded LayerNorm (whole 8-column groups only: its column terms are loaded 8 at a time), softmax partials
-  return p.nsplit == 1 && (e.ldc & 7) == 0 && (!e.ln_stats || p.N % 8 == 0);
+  if (!(p.nsplit == 1 && (e.ldc & 7) == 0 && (!e.ln_stats || p.N % 8 == 0))) return -1;
+  return 2 + (e.rowstat ? 1 : 0) + (e.ln_stats ? 4 : 0);
 }
-void launch_gemm_w4(const LaunchTable& tab, hipStream_t s) {
-  const EpiArgs& e = tab.p[0].epi;
-  if (e.c_f32) { launch_w4<8>(tab, s); return; }
-  const int epi = 2 + (e.rowstat ? 1 : 0) + (e.ln_stats ? 4 : 0);
-  switch (epi) {
+void launch_gemm_w4(const LaunchTable& tab, const GemmDecision& d, hipStream_t s) {
+  switch (d.epi) {
+    case 8: launch_w4<8>(tab, s); break;
     case 2: launch_w4<2>(tab, s); break;
     case 3: launch_w4<3>(tab, s); break;
     case 6: launch_w4<6>(tab, s); break;

@@ -118,16 +118,17 @@ def get_cu_budget() -> int:
     return int(L.lib().mic_get_cu_budget())
 
 
-def gemm_plan(shapes, *, a_kmajor=False, b_kmajor=False, split_k=0, dtype=None) -> dict:
+def gemm_plan(shapes, *, a_kmajor=False, b_kmajor=False, split_k=0, dtype=None, kernel=False) -> dict:
     """What the planner would launch for the problems [(M, N, K), ...] of one grouped bf16 launch under the current CU budget
-    (host arithmetic; nothing runs and no device memory is needed)."""
+    (host arithmetic; nothing runs and no device memory is needed).  kernel=True: also which kernel runs ("family": an index into
+    _lib.GEMM_FAMILIES, "plain", "epi": include/mic_hip.h)."""
     arr = (L.GemmArgs * len(shapes))()
     for g, (M, N, K) in zip(arr, shapes):
         g.dtype = g.c_dtype = L.MIC_BF16 if dtype is None else dtype
         g.M, g.N, g.K, g.a_kmajor, g.b_kmajor, g.split_k = M, N, K, int(a_kmajor), int(b_kmajor), int(split_k)
     out = L.GemmPlanInfo()
     L.check(L.lib().mic_gemm_plan(arr, len(shapes), C.byref(out)), "mic_gemm_plan")
-    return {k: getattr(out, k) for k, _ in L.GemmPlanInfo._fields_}
+    return {k: getattr(out, k) for k, _ in L.GemmPlanInfo._fields_ if kernel or k not in ("family", "plain", "epi")}
 
 
 def comm_emulate(src: torch.Tensor, dst: torch.Tensor, nbytes: int, micros: float, blocks: int):

@@ -164,7 +164,10 @@ def test_case_plan_claims(name):
     try:
         if c["cus"]:
             ops.set_cu_budget(c["cus"])
-        assert GC.plan_of(c) == c["plan"]
+        rep = GC.plan_report(c)
+        assert {k: rep[k] for k in c["plan"]} == c["plan"]
+        # ... and the report names the instantiation the case claims (the launcher launches what the same decision says)
+        assert GC.kernel_name(rep, c["dtype"], c["akm"], c["bkm"]) == c["kernel"], rep
     finally:
         ops.set_cu_budget(0)
 
@@ -180,5 +183,6 @@ def test_coverage_of_the_product_profiles():
     assert len(prod) >= 20
     missing = prod - _instantiations(COVERAGE_PROFILE)
     assert not missing, sorted(missing)
-    claimed = {re.sub(r"\s+", "", c["kernel"]) for c in GC.CASES if c["kernel"]}
+    assert all(c["kernel"] for c in GC.CASES)
+    claimed = {re.sub(r"\s+", "", c["kernel"]) for c in GC.CASES}
     assert claimed <= _instantiations(COVERAGE_PROFILE), sorted(claimed - _instantiations(COVERAGE_PROFILE))

@@ -369,13 +369,13 @@ def run_case(c, dev, *, seed=0, check_plan=True, rerun=True):
         arr = (L.GemmArgs * min(len(args), 8))(*args[:8])
         info = L.GemmPlanInfo()
         L.check(L.lib().mic_gemm_plan(arr, len(arr), C.byref(info)), "mic_gemm_plan")
-        got = {k: getattr(info, k) for k in list(c["plan"]) + ["blocks"]}
+        got = {k: getattr(info, k) for k, _ in L.GemmPlanInfo._fields_}
         switch = os.environ.get("MIC_GEMM_CONF_SWITCH")
         if switch:
             assert GC.switch_honoured(switch, c, got), (c["name"], switch, got)
         else:
-            del got["blocks"]
-            assert got == c["plan"], (c["name"], got, c["plan"])
+            assert {k: got[k] for k in c["plan"]} == c["plan"], (c["name"], got, c["plan"])
+            assert GC.kernel_name(got, c["dtype"], c["akm"], c["bkm"]) == c["kernel"], (c["name"], got)
     _launch(probs, c["group"] is not None)
     worst = {}
     for i, p in enumerate(probs):

@@ -810,6 +810,12 @@ def test_gemm_192_row_tiles(dev, M, N, K):
 
 
 
+def _tile_n_of_a_bare_256_row_launch(K):
+    """tile columns mic_gemm_plan reports for a single bf16 NT problem with 256-row tiles and a bare epilogue: 256 — or 128 where
+    MIC_GEMM_D2=2 hands the launch to gemm_d2.hip (256 x 128 tiles, K >= 128): the report names the kernel that runs"""
+    return 128 if os.environ.get("MIC_GEMM_D2") == "2" and K >= 128 else 256
+
+
 @pytest.mark.parametrize("M,N,K", [(2048, 16384, 192), (1000, 66048, 64), (1024, 131072, 1024), (3200, 24576, 1024), (600, 98304, 128)])
 def test_gemm_phased_many_tiles(dev, M, N, K):
     """the LDS-DMA 256 x 256 kernel on single NT problems with several tiles per CU: odd and even K-tile counts, a single K-tile,
@@ -820,7 +826,7 @@ def test_gemm_phased_many_tiles(dev, M, N, K):
 
     plan = ops.gemm_plan([(M, N, K)])
     w4 = os.environ.get("MIC_GEMM_W4", "1") != "0" and K >= 256 and K % 128 == 0  # (the four-wave kernel takes these shapes by default)
-    assert plan["tile"] == 256 and plan["phased"] == (2 if w4 else 1) and plan["blocks"] > 256
+    assert plan["tile_m"] == 256 and plan["tile"] == _tile_n_of_a_bare_256_row_launch(K) and plan["phased"] == (2 if w4 else 1) and plan["blocks"] > 256
     dt = torch.bfloat16
     g = torch.Generator().manual_seed(M + N + K)
     A, B = rnd((M, K), g, dt), rnd((N, K), g, dt, 0.1)
@@ -861,7 +867,8 @@ def test_gemm_layernorm_fold_with_softmax_partials(dev):
     from mic_amd import ops
 
     M, N, K = 600, 66048, 256
-    assert ops.gemm_plan([(M, N, K)])["tile"] == 256
+    plan = ops.gemm_plan([(M, N, K)])  # (the bare shape; with the folded LayerNorm the launch stays off gemm_d2.hip)
+    assert plan["tile_m"] == 256 and plan["tile"] == _tile_n_of_a_bare_256_row_launch(K)
     g = torch.Generator().manual_seed(7)
     dt = torch.bfloat16
     x = (rnd((M, K), g, dt, 1.0) + 0.5).to(dev)
@@ -999,7 +1006,8 @@ def test_gemm_four_wave_kernel_repeats_bit_for_bit(dev, M, N, K):
     overlap on two streams and when the last row tile is partial (waves whose rows lie past M idle through the K loop)"""
     from mic_amd import ops
 
-    assert ops.gemm_plan([(M, N, K)])["tile"] == 256 and ops.gemm_plan([(M, N, K)])["blocks"] > 256
+    plan = ops.gemm_plan([(M, N, K)])
+    assert plan["tile_m"] == 256 and plan["tile"] == _tile_n_of_a_bare_256_row_launch(K) and plan["blocks"] > 256
     g = torch.Generator().manual_seed(M + K)
     a, b = rnd((M, K), g, torch.bfloat16).to(dev), rnd((N, K), g, torch.bfloat16, 0.1).to(dev)
     bias = torch.randn(N, generator=g).to(dev)

@@ -4,7 +4,7 @@ so a planner change that moves a case off its kernel fails a test instead of shr
 
 A case: shape (M, N, K), operand layout (akm = a_kmajor, bkm = b_kmajor), dtype ("bf16" / "e4m3" / "e5m2": fp8 with A in
 that format, B e4m3), the CU budget (0 = default), the epilogue features, the plan it targets and the kernel that plan
-launches (a comment-level claim; the committed coverage profile is what proves it).  `group`: a grouped launch, one feature
+launches (asserted against the name mic_gemm_plan's report spells, kernel_name below, and against the committed coverage profile).  `group`: a grouped launch, one feature
 dict per problem.
 
 Features: alpha, bias, act, zout, dact, drop (p), res, acc, c32 (fp32 C), split (split_k), slabs (split-K into fp32 slabs +
@@ -108,9 +108,9 @@ CASES = [
     case("fp8c_fc1_gelu_e4m3", 2404, 4096, 1024, dtype="e4m3", bias=1, act=1, zout=1, c8="e4m3", c8_amax=96.0,
          plan=P(128, 128, 1, 0, 608, 2), kernel="gemm_bf16_kernel<64,32,4,64,false,false,1,false,1>", tags=("kg128", "tile")),
     case("fp8c_fc2_dx_dgelu_e5m2", 2404, 1024, 4096, dtype="e5m2", dact=1, c8="e5m2", c8_amax=160.0,
-         plan=P(128, 128, 2, 0, 152, 1), kernel="", tags=("kg128",)),
+         plan=P(128, 128, 2, 0, 152, 1), kernel="gemm_bf16_kernel<64,32,4,64,false,false,2,false,2>", tags=("kg128",)),
     case("fp8c_decode_gelu_64", 1024, 1024, 1024, dtype="e4m3", bias=1, act=2, zout=1, c8="e4m3", c8_amax=80.0,
-         plan=P(64, 64, 2, 0, 256, 2), kernel="", tags=("kg", "tile")),
+         plan=P(64, 64, 2, 0, 256, 2), kernel="gemm_bf16_kernel<32,32,2,64,false,false,2,false,1>", tags=("kg", "tile")),
     # ---- features the product does not launch today (header-admitted)
     case("alpha_bias_act_dropout_res", 2404, 1024, 1024, alpha=0.375, bias=1, act=2, zout=1, drop=0.5, res=1,
          plan=P(128, 128, 2, 0, 152, 1), kernel="gemm_bf16_kernel<64,32,4,64,false,false,2,false,0>", tags=("kg128",)),
@@ -154,12 +154,16 @@ CASES = [
          kernel="gemm_bf16_kernel<32,32,2,64,true,true,1,true,0>",
          group=[dict(M=64 * (1 + i % 3), N=128, K=320, c32=1, rowsum=1, k_valid=300 - 5 * i) for i in range(11)]),
     # ---- ragged edges, one K-tile
-    case("edge_m1_n1", 1, 1, 64, bias=1, plan=P(64, 64, 1, 0, 1, 4), kernel="", tags=("kg",)),
-    case("edge_m63_n65", 63, 65, 64, bias=1, act=1, zout=1, plan=P(64, 64, 1, 0, 2, 4), kernel="", tags=("kg",)),
-    case("edge_m129_n127", 129, 127, 128, bias=1, res=1, plan=P(64, 64, 1, 0, 6, 4), kernel="", tags=("kg",)),
+    case("edge_m1_n1", 1, 1, 64, bias=1, plan=P(64, 64, 1, 0, 1, 4), kernel="gemm_bf16_kernel<32,32,2,64,false,false,1,false,0>",
+         tags=("kg",)),
+    case("edge_m63_n65", 63, 65, 64, bias=1, act=1, zout=1, plan=P(64, 64, 1, 0, 2, 4),
+         kernel="gemm_bf16_kernel<32,32,2,64,false,false,1,false,0>", tags=("kg",)),
+    case("edge_m129_n127", 129, 127, 128, bias=1, res=1, plan=P(64, 64, 1, 0, 6, 4),
+         kernel="gemm_bf16_kernel<32,32,2,64,false,false,1,false,0>", tags=("kg",)),
     case("edge_m120_n248_kmajor", 120, 248, 64, akm=True, bkm=True, c32=1, rowsum=1, k_valid=40, plan=P(64, 64, 1, 0, 8, 4),
-         kernel="", tags=("kg",)),
-    case("edge_m257_n255_256tile", 257, 255, 64, bias=1, cus=0, plan=P(64, 64, 1, 0, 20, 4), kernel="", tags=("tile",)),
+         kernel="gemm_bf16_kernel<32,32,2,64,true,true,1,true,0>", tags=("kg",)),
+    case("edge_m257_n255_256tile", 257, 255, 64, bias=1, cus=0, plan=P(64, 64, 1, 0, 20, 4),
+         kernel="gemm_bf16_kernel<32,32,2,64,false,false,1,false,0>", tags=("tile",)),
 ]
 
 # budgets under which the persistent 256^2 grid and the K-group variants run with their results checked
@@ -202,6 +206,7 @@ def plan_args(c):
         g.M, g.N, g.K, g.a_kmajor, g.b_kmajor = M, N, K, int(c["akm"]), int(c["bkm"])
         off = 2 if f.get("off") else 0
         g.A = g.B = fake
+        g.lda, g.ldb = (M if c["akm"] else K), (N if c["bkm"] else K)
         g.C, g.ldc = fake + off, ld_of(N, f)
         g.bias = fake if f.get("bias") or f.get("ln") else None
         g.act, g.dact = f.get("act", 0), f.get("dact", 0)
@@ -218,16 +223,37 @@ def plan_args(c):
         g.a_rowsum = fake if f.get("rowsum") else None
         g.rowstat = fake if f.get("rowstat") else None
         g.k_valid = f.get("k_valid", 0)
+        if f.get("ln"):
+            g.a_ln_stats, g.a_ln_colsum, g.a_ln_width = fake, fake, K
+        g.rowsum2 = fake if f.get("rowsum2") else None
     return arr
 
 
+def kernel_name(rep: dict, dtype: str, akm, bkm) -> str:
+    """the kernel instantiation a plan report (mic_gemm_plan: family, tiling, K-groups, PLAIN, epilogue variant) names, as the
+    kernel traces print it (without blanks)"""
+    from mic_amd import _lib as L
+
+    b = lambda x: "true" if x else "false"  # noqa: E731
+    fam = L.GEMM_FAMILIES[rep["family"]]
+    if fam in ("w4", "d2"):
+        return f"gemm_{fam}_kernel<{rep['epi']}>"
+    if fam == "phased":
+        return f"gemm_phased_kernel<{b(akm)},{b(bkm)},{b(rep['plain'])}>"
+    wn, wnw = {256: (64, 4), 128: (32, 4), 64: (32, 2)}[rep["tile"]]
+    f8 = {"bf16": 0, "e4m3": 1, "e5m2": 2}[dtype]
+    return f"gemm_bf16_kernel<{rep['tile_m'] // 2},{wn},{wnw},64,{b(akm)},{b(bkm)},{rep['kgroups']},{b(rep['plain'])},{f8}>"
+
+
 def switch_honoured(switch: str, c, got: dict) -> bool:
-    """does the plan `got` (mic_gemm_plan under the latched switch, with "blocks") follow MIC_GEMM_*=value for case c?  MIC_GEMM_D2=2
-    only changes which kernel takes a launch at run time, the plan cannot show it"""
+    """does the report `got` (every field of mic_gemm_plan under the latched switch) follow MIC_GEMM_*=value for case c?"""
+    from mic_amd import _lib as L
+
     env, val = switch.split("=")
     v = int(val)
     fp8 = c["dtype"] != "bf16"
     f = c["feats"]
+    fam = L.GEMM_FAMILIES[got["family"]]
     if env == "MIC_GEMM_TILE":
         if f.get("rowstat"):
             return True  # softmax partials force the 256-wide configuration
@@ -238,20 +264,117 @@ def switch_honoured(switch: str, c, got: dict) -> bool:
     if env == "MIC_GEMM_KG128":
         return not (got["tile"] == 128 and got["tile_m"] == 128) or got["kgroups"] == v
     if env == "MIC_GEMM_T192":
-        return got["tile_m"] != 192
+        return got["tile_m"] != 192 and fam != "t192"
     if env == "MIC_GEMM_PERSIST":
         return got["grid"] == got["blocks"]
     if env == "MIC_GEMM_W4":
-        return got["phased"] != 2
+        return got["phased"] != 2 and fam not in ("w4", "d2")  # (the default MIC_GEMM_D2=3 only takes what the four-wave kernel would)
     if env == "MIC_GEMM_D2":
-        return v == 2 or not (got["tile"] == 128 and got["tile_m"] == 256)
+        d2_tiling = got["tile"] == 128 and got["tile_m"] == 256
+        if v == 0:
+            return fam != "d2" and not d2_tiling
+        # 2: every single-problem bf16 NT launch with 256-row tiles whose epilogue gemm_d2.hip covers (no folded LayerNorm, no rowsum2,
+        # whole 8-column units with 16-B aligned rows everywhere)
+        nt1 = not fp8 and not c["akm"] and not c["bkm"] and not c["group"] and got["tile_m"] == 256
+        want = nt1 and not (f.get("ln") or f.get("rowsum2") or f.get("off")) and ld_of(c["N"], f) % 8 == 0 and c["N"] % 8 == 0
+        return (fam == "d2") == bool(want) and d2_tiling == (fam == "d2")
     raise AssertionError(switch)
 
 
-def plan_of(c) -> dict:
+def plan_report(c) -> dict:
+    """every field of mic_gemm_plan's report for a case"""
     from mic_amd import _lib as L
 
     arr = plan_args(c)
     out = L.GemmPlanInfo()  # (a group of more than 8 problems: the plan of its first launch)
     L.check(L.lib().mic_gemm_plan(arr, min(len(arr), 8), C.byref(out)), "mic_gemm_plan")
-    return {k: getattr(out, k) for k in ("tile", "tile_m", "kgroups", "phased", "grid", "blocks_per_cu")}
+    return {k: getattr(out, k) for k, _ in L.GemmPlanInfo._fields_}
+
+
+def plan_of(c) -> dict:
+    rep = plan_report(c)
+    return {k: rep[k] for k in ("tile", "tile_m", "kgroups", "phased", "grid", "blocks_per_cu")}
+
+
+# ---- the recorded planner sweep (tests/golden/gemm_plan_parent.npz, written by tests/golden/make_golden_gemm_plan.py on the commit
+# before the dispatch decision moved into one function): drawn argument sets and that commit's mic_gemm_plan answers.
+#   draws  [n][7]: first problem row, problem count, dtype (0 bf16, 1 e4m3, 2 e5m2), a_kmajor, b_kmajor, CU budget (0 = default),
+#                  switch block (0 = default switches, i + 1 = SWITCHES[i])
+#   probs  [m][8]: M, N, K, ldc, feature bits (F_*), activation id (act, or dact with F_DACT), split_k, fp8-C format + 1 (0 = none)
+#   answers [n][9]: return code and the eight fields of ANSWER_FIELDS
+PLAN_FIXTURE = "golden/gemm_plan_parent.npz"
+F_C32, F_BIAS, F_ZOUT, F_DACT, F_RES, F_ACC, F_ROWSTAT, F_ROWSUM, F_OFF, F_SLABS = (1 << i for i in range(10))
+ANSWER_FIELDS = ("tile", "kgroups", "blocks", "grid", "blocks_per_cu", "phased", "cu_budget", "tile_m")
+
+
+def draw_args(d, probs):
+    """mic_gemm_args of one recorded draw (stand-in pointers, never dereferenced; every argument set passes mic_gemm's host checks)"""
+    from mic_amd import _lib as L
+
+    fake = 1 << 24
+    first, count, dt, akm, bkm = (int(x) for x in d[:5])
+    arr = (L.GemmArgs * count)()
+    for g, row in zip(arr, probs[first:first + count]):
+        M, N, K, ldc, fl, actid, split, c8 = (int(x) for x in row)
+        g.dtype = L.MIC_FP8 if dt else L.MIC_BF16
+        g.c_dtype = L.MIC_FP8 if c8 else (L.MIC_F32 if fl & F_C32 else L.MIC_BF16)
+        g.a_fmt, g.b_fmt = (L.MIC_E5M2 if dt == 2 else L.MIC_E4M3), L.MIC_E4M3
+        g.M, g.N, g.K, g.a_kmajor, g.b_kmajor = M, N, K, akm, bkm
+        g.A, g.lda, g.B, g.ldb = fake, (M if akm else K), fake, (N if bkm else K)
+        off = 2 if fl & F_OFF else 0
+        g.C, g.ldc = fake + off, ldc
+        g.bias = fake if fl & F_BIAS else None
+        g.act, g.dact = (0, actid) if fl & F_DACT else (actid, 0)
+        g.Zout = fake + off if fl & F_ZOUT else None
+        g.Zin = fake + off if fl & F_DACT else None
+        g.ldz = ldc
+        if fl & F_RES:
+            g.R, g.ldr = fake + off, ldc
+        g.accumulate = int(bool(fl & F_ACC))
+        g.split_k = split
+        g.split_stride = (M * ldc + 63) // 64 * 64 if fl & F_SLABS else 0
+        g.a_rowsum = fake if fl & F_ROWSUM else None
+        if fl & F_ROWSTAT:
+            g.rowstat, g.rowstat_ld = fake, N // 64
+        if c8:
+            g.c_q8_state, g.c_q8_fmt = fake, c8 - 1
+    return arr
+
+
+def plan_answers(draws, probs, rows):
+    """[rc, *ANSWER_FIELDS] of mic_gemm_plan for the draws `rows`, each under its recorded CU budget (this process's latched switches)"""
+    from mic_amd import _lib as L
+
+    lib = L.lib()
+    out = []
+    try:
+        for r in rows:
+            d = draws[r]
+            L.check(lib.mic_set_cu_budget(int(d[5])), "mic_set_cu_budget")
+            info = L.GemmPlanInfo()
+            rc = lib.mic_gemm_plan(draw_args(d, probs), int(d[1]), C.byref(info))
+            out.append([rc] + [getattr(info, k) for k in ANSWER_FIELDS])
+    finally:
+        lib.mic_set_cu_budget(0)
+    return out
+
+
+if __name__ == "__main__":  # child process of the equivalence test: replay one switch block, print the rows that differ
+    import json
+    import os
+    import sys
+
+    import numpy as np
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.dirname(here))
+    fx = np.load(os.path.join(here, PLAN_FIXTURE))
+    block = int(sys.argv[1])
+    rows = np.nonzero(fx["draws"][:, 6] == block)[0]
+    got = plan_answers(fx["draws"], fx["probs"], rows)
+    bad = [(int(r), g, fx["answers"][r].tolist()) for r, g in zip(rows, got) if g != fx["answers"][r].tolist()]
+    ignored = []  # ... and the conformance cases this block's switch can change: does the report follow the switch?
+    if block:
+        env, val, tag = SWITCHES[block - 1]
+        ignored = [c["name"] for c in CASES if tag in c["tags"] and not switch_honoured(f"{env}={val}", c, plan_report(c))]
+    print(json.dumps({"replayed": len(rows), "differ": len(bad), "first": bad[:5], "switch_ignored": ignored}))
