@@ -208,8 +208,8 @@ int mic_fp8_roll_amax(float* state, int stride_floats, float* partials, int coun
  * fp8(round_bf16(x[r][c]) * FMAX / state[0]) with state[0] the amax the tensor had in the previous pass (mic_fp8_roll_amax), records
  * this pass's max |x| in amax_next (as mic_fp8_quantize does under delayed scaling) and writes state[1] = state[0] / FMAX, the
  * dequantisation factor mic_gemm multiplies back.  Same bytes as producer + mic_fp8_quantize on the same scale; one launch less per
- * tensor (the step had 181 of them).  Producers: mic_layernorm_fwd_q8, mic_layernorm_bwd_partials_q8, mic_attn_bwd_q8 /
- * mic_attn_bwd_packed_q8 and the epilogue of an fp8 mic_gemm (mic_gemm_args.c_q8).  No reference counterpart (configs[4]). */
+ * tensor (the step had 181 of them).  Producers: mic_layernorm_fwd_q8, mic_layernorm_bwd_partials_q8, mic_attn_bwd_q8 (dense and
+ * packed rows) and the epilogue of an fp8 mic_gemm (mic_gemm_args.c_q8).  No reference counterpart (configs[4]). */
 typedef struct {
   void* q; int ldq;      /* fp8 bytes [rows][ldq], ldq % 8 == 0, 8-B aligned */
   float* state;          /* [2]: amax of the previous pass (read), 1 / scale (written) */
@@ -255,8 +255,13 @@ int mic_ln_param_grads(const mic_ln_param_item* items, int count, void* stream);
  * Attention core (flax dot_product_attention_weights): q scaled by 1/sqrt(D) first,
  * softmax(q k^T + bias) v, heads merged.  q [B*Tq][ldq], k/v [B*Tk][ldk/ldv] with head h at column
  * h*64 (head_dim is 64 for both models); out [B*Tq][ldo].  causal: key j allowed iff j <= i.
- * key_mask int32 [B][Tk] (1 = attend) or NULL.  Disallowed -> -inf bias.  lse [B][H][Tq] saved for bwd.
- * Tq, Tk <= 64.  Covers K4 (ViT, 50x50), K9 (decoder causal+padding, 64x64), K10 (cross, 64x50).
+ * key_mask int32 [B][Tk] (1 = attend) or NULL.  Disallowed -> -inf bias.  lse [B][H][Tq] saved for bwd
+ * (may be NULL in fwd).  Tq, Tk <= 64: one 64x64 tile per (batch, head) — K4 (ViT, 50x50), K9 (decoder
+ * causal+padding, 64x64), K10 (cross, 64x50); above 64 in either: the tiled kernels (online softmax over
+ * 64-key blocks, two-pass backward), any Tq, Tk.  Row strides of q, k, v (bwd: out, dout too) keep 16-B
+ * alignment.  A query row with no admissible key (e.g. causal with key_mask[b][0] == 0, or a batch entry
+ * masked entirely): its out row is 0, its lse is -inf, and bwd adds nothing for it to dQ / dK / dV (its dQ
+ * row is 0; every gradient stays finite).  bwd reads out and lse as the forward stored them.
  * ------------------------------------------------------------------------------------------- */
 int mic_attn_fwd(int dtype, int B, int H, int Tq, int Tk, const void* q, int ldq, const void* k, int ldk,
                  const void* v, int ldv, void* out, int ldo, const int32_t* key_mask, int causal, float* lse,
@@ -268,7 +273,8 @@ int mic_attn_bwd(int dtype, int B, int H, int Tq, int Tk, const void* q, int ldq
 
 /* The attention weights themselves, for `output_attentions=True` (modeling:499-510 forwards the flag to the Flax modules, which
  * return every layer's softmax weights): out[B][H][Tq][Tk] (fp32) = softmax over the keys of q.k / sqrt(64) with the masks of
- * mic_attn_fwd.  A diagnostic kernel (one wave per query row), never launched by the train / generate paths.  Tk <= 1024. */
+ * mic_attn_fwd; disallowed pairs, and every pair of a query row with no admissible key, are exact zeros.  A diagnostic kernel
+ * (one wave per query row), never launched by the train / generate paths.  Tk <= 1024. */
 int mic_attn_probs(int dtype, int B, int H, int Tq, int Tk, const void* q, int ldq, const void* k, int ldk,
                    const int32_t* key_mask, int causal, float* out, void* stream);
 
@@ -276,7 +282,8 @@ int mic_attn_probs(int dtype, int B, int H, int Tq, int Tk, const void* q, int l
  * [sum q_len][ld] matrix — padded positions have no rows at all (their loss weight is 0 and no valid position attends to them,
  * main.py:678, 692: every gradient they would contribute is exactly 0).  kv_packed = 1: keys / values are the same packed rows
  * (decoder self-attention: key j allowed iff j <= i, all within q_len[b]); kv_packed = 0: every sequence has its Tk dense rows
- * [b*Tk, (b+1)*Tk) (cross-attention over the encoder states).  q_len[b] <= Tq_max <= 64, Tk <= 64; lse [B][H][Tq_max]. */
+ * [b*Tk, (b+1)*Tk) (cross-attention over the encoder states).  1 <= q_len[b] <= Tq_max <= 64, Tk <= 64 (refused otherwise);
+ * lse [B][H][Tq_max]: the entries lse[b][h][i], i >= q_len[b], are not written (fwd) and not read (bwd). */
 int mic_attn_fwd_packed(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
                         const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, int causal,
                         float* lse, void* stream);
@@ -296,7 +303,8 @@ int mic_attn_bwd_q8(int B, int H, int Tq, int Tk, const int32_t* q_off, const in
  * reordered by beam (gen:945-953): src_row [R][max_len] int32 says in which row slot s of row r's
  * history lives (beam-parent indirection); NULL = row r reads cache row r / row_div (cross-attention K/V are
  * computed once per image and shared by its beams: row_div = num_beams, cur = S-1).  kc/vc: [rows][max_len] slots of
- * ldc elements each (ldc = H*64 for the self cache; 2*H*64 when k and v are the halves of a fused projection). */
+ * ldc elements each (ldc = H*64 for the self cache; 2*H*64 when k and v are the halves of a fused projection).  The slots
+ * read are 0 .. min(cur + 1, max_len) - 1; ldq, ldc, ldo keep 16-B alignment. */
 int mic_attn_decode(int dtype, int R, int H, int max_len, int cur, const void* q, int ldq, const void* kc,
                     const void* vc, int ldc, const int32_t* src_row, int row_div, void* out, int ldo, void* stream);
 /* writes this step's k,v (columns of the fused qkv projection) into slot `cur` of every row's own cache */

@@ -173,13 +173,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(int H, int Tq_max, int Tk
   if (lane < 32) pmax[jb * 64 + i] = m;
   __syncthreads();
   const float mrow = fmaxf(pmax[i], pmax[64 + i]);
+  const float m_safe = mrow == -INFINITY ? 0.f : mrow;  // a row with no admissible key: p = 0, not NaN
   float l = 0.f;
 #pragma unroll
   for (int g4 = 0; g4 < 4; ++g4) {
     float pv[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float p = __expf(s[g4 * 4 + e] - mrow);
+      const float p = __expf(s[g4 * 4 + e] - m_safe);
       pv[e] = p;
       l += p;
     }
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(int H, int Tq_max, int Tk
   l += __shfl_xor(l, 32, 64);
   if (lane < 32) psum[jb * 64 + i] = l;
   __syncthreads();
+  // (a row with no admissible key: lse = -inf + log 0 = -inf, and its output row is 0 — the backward then adds nothing for it)
   if (jb == 0 && lane < 32 && i < Tq && lse_out) lse_out[((size_t)b * H + h) * Tq_max + i] = mrow + logf(psum[i] + psum[64 + i]);
   {
     const int db = wave & 1;  // output block (ib, db)
@@ -199,7 +201,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(int H, int Tq_max, int Tk
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int qi = ib * 32 + acc_row(r, lane);
-        if (qi < Tq) ElemT<T>::st(out + (q0 + qi) * ldo + h * 64 + d, o[r] / (psum[qi] + psum[64 + qi]));
+        const float lq = psum[qi] + psum[64 + qi];
+        if (qi < Tq) ElemT<T>::st(out + (q0 + qi) * ldo + h * 64 + d, lq > 0.f ? o[r] / lq : 0.f);
       }
     }
   }
@@ -444,7 +447,8 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(int H, int Tq, int 
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int qi = ib * 32 + acc_row(r, lane);
-    if (qi < nq) ElemT<T>::st(out + ((size_t)b * Tq + q0 + qi) * ldo + h * 64 + d, o[r] / l_run[qi]);
+    const float lq = l_run[qi];  // 0: a row with no admissible key in any block -> output row 0, lse -inf
+    if (qi < nq) ElemT<T>::st(out + ((size_t)b * Tq + q0 + qi) * ldo + h * 64 + d, lq > 0.f ? o[r] / lq : 0.f);
   }
 }
 
@@ -627,7 +631,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(int n_rows, int H, int 
     sum += sc[i];
   }
   sum = wave_sum(sum);
-  const float inv = 1.0f / sum;
+  const float inv = sum > 0.f ? 1.0f / sum : 0.f;  // a row with no admissible key: all zeros
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int sidx = i * 64 + lane;
@@ -985,6 +989,10 @@ extern "C" int mic_attn_decode(int dtype, int R, int H, int max_len, int cur, co
                                const void* vc, int ldc, const int32_t* src_row, int row_div, void* out, int ldo, void* stream) {
   MIC_CHECK(R > 0 && H > 0 && max_len > 0 && cur >= 0 && row_div >= 1, "mic_attn_decode: bad shape R=%d H=%d max_len=%d cur=%d", R, H, max_len, cur);
   MIC_CHECK(q && kc && vc && out, "mic_attn_decode: null pointer");
+  {
+    const int align = dtype == MIC_BF16 ? 8 : 4;  // 16-B loads of q / k / v and stores of out
+    MIC_CHECK(ldq % align == 0 && ldc % align == 0 && ldo % align == 0, "mic_attn_decode: row strides must keep 16-B alignment");
+  }
   const bool chunked = (cur + 1 < max_len ? cur + 1 : max_len) > 64;
   if (!src_row && !chunked && (row_div == 2 || row_div == 4 || row_div == 8) && R % row_div == 0) {
     // the beams of an image share keys and values: one wave per (image, head) serves all of them
