@@ -490,6 +490,20 @@ typedef struct {
 } mic_beam_step_args;
 int mic_beam_step(const mic_beam_step_args* a, void* stream);
 
+/* Several searches in one decode chain (generate() with a sequence of language ids = that many separate calls on the same images).
+ * mic_row_forced_topk: the forced-token branch of mic_row_lse_topk with the token read per row — ForcedBOS at cur_len == 1
+ *   (gen:412-419) when the rows of one launch belong to calls with different forced ids.  Entry 0 of row r is
+ *   (0 + row_bias[r], forced_rows[r]), entries 1..k-1 are -inf with the lowest indices that skip the forced one; reads no logits.
+ *   forced_rows[r] must be a valid token id (>= 0).
+ * mic_beam_step_groups: mic_beam_step over a->B items of which item i belongs to search i % groups (a->B a multiple of groups).
+ *   a->gstate is [groups][8], zeroed by the caller: a search's items look only at its own done flag, add to its own counters, and the
+ *   last of its a->B / groups arrivals evaluates beam_search_cond_fn (gen:798-820) over that search alone and bumps its step count.
+ *   The state of a search that has ended (sequences, scores, src_row, next_token) is left alone by later launches.  groups == 1 is
+ *   mic_beam_step. */
+int mic_row_forced_topk(int R, int k, const int32_t* forced_rows, const float* row_bias, float* top_val, int32_t* top_idx,
+                        void* stream);
+int mic_beam_step_groups(const mic_beam_step_args* a, int groups, void* stream);
+
 int mic_greedy_step(int B, int max_len, int cur_len, int eos_token_id, int pad_token_id, const int32_t* top_idx,
                     int ld_top, int32_t* sequences, int32_t* finished, int32_t* next_token, void* stream);
 

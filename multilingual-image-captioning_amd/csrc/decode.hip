@@ -9,6 +9,14 @@
 
 __device__ __forceinline__ bool better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 
+// ForcedBOS / ForcedEOS (gen:412-419): everything -inf except the forced token := 0 (+ running score); lax.top_k then lists the
+// lowest indices among the -inf ties.  Entry t of a row's k candidates.
+__device__ __forceinline__ void forced_entry(int forced, int t, float bias, float& val, int& idx) {
+  idx = forced;
+  if (t > 0) { idx = t - 1; if (idx >= forced) ++idx; }
+  val = t == 0 ? 0.f + bias : -INFINITY;
+}
+
 // ------------------------------------------------------------------ per-row lse + top-k
 // One 256-thread block per row of the [R][ld] logits.  Pass 1 streams the row once: online (max, sum-exp) and each
 // thread's own maximum.  The 8th largest of the 256 thread maxima is a provable lower bound tau on the row's k-th best
@@ -19,20 +27,21 @@ __device__ __forceinline__ bool better(float av, int ai, float bv, int bi) { ret
 template <typename T, int KMAX>
 __global__ __launch_bounds__(256) void row_lse_topk_kernel(int V, const T* __restrict__ logits, int ld, int k, int forced,
                                                            int suppress_eos, int eos, int raw, const float* __restrict__ row_bias,
-                                                           float* __restrict__ top_val, int32_t* __restrict__ top_idx) {
+                                                           float* __restrict__ top_val, int32_t* __restrict__ top_idx,
+                                                           const int32_t* __restrict__ forced_rows) {
   __shared__ float sm[256], ss[256];
   __shared__ int si[256];
   const int row = blockIdx.x, tid = threadIdx.x;
   const T* lr = logits + (size_t)row * ld;
   const int nchunk = (V + 7) >> 3;
   const float bias = row_bias ? row_bias[row] : 0.f;
+  if (forced_rows) forced = forced_rows[row];  // the rows of this launch belong to calls with different forced ids (mic_row_forced_topk)
   if (forced >= 0) {
-    // ForcedBOS / ForcedEOS: everything -inf except the forced token := 0 (+ running score); lax.top_k then lists the
-    // lowest indices among the -inf ties.  No scan needed.
+    // no scan needed
     if (tid < k) {
-      int idx = forced;
-      if (tid > 0) { idx = tid - 1; if (idx >= forced) ++idx; }
-      top_val[(size_t)row * k + tid] = tid == 0 ? 0.f + bias : -INFINITY;
+      float val; int idx;
+      forced_entry(forced, tid, bias, val, idx);
+      top_val[(size_t)row * k + tid] = val;
       top_idx[(size_t)row * k + tid] = idx;
     }
     return;
@@ -190,11 +199,22 @@ extern "C" int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int
                                 int32_t* top_idx, void* stream) {
   MIC_CHECK(R > 0 && V > 0 && ld >= V && ld % 8 == 0 && k >= 1 && k <= TOPK_WIDE && logits && top_val && top_idx, "mic_row_lse_topk: bad args (k <= 64)");
   dim3 grid(R), block(256);
-#define TOPK_LAUNCH(TT, KM) hipLaunchKernelGGL((row_lse_topk_kernel<TT, KM>), grid, block, 0, (hipStream_t)stream, V, (const TT*)logits, ld, k, forced_token, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx)
+#define TOPK_LAUNCH(TT, KM) hipLaunchKernelGGL((row_lse_topk_kernel<TT, KM>), grid, block, 0, (hipStream_t)stream, V, (const TT*)logits, ld, k, forced_token, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx, (const int32_t*)nullptr)
   if (dtype == MIC_BF16) { if (k <= 8) TOPK_LAUNCH(uint16_t, 8); else if (k <= 16) TOPK_LAUNCH(uint16_t, 16); else if (k <= 32) TOPK_LAUNCH(uint16_t, 32); else TOPK_LAUNCH(uint16_t, 64); }
   else if (dtype == MIC_F32) { if (k <= 8) TOPK_LAUNCH(float, 8); else if (k <= 16) TOPK_LAUNCH(float, 16); else if (k <= 32) TOPK_LAUNCH(float, 32); else TOPK_LAUNCH(float, 64); }
   else MIC_CHECK(false, "mic_row_lse_topk: bad dtype");
 #undef TOPK_LAUNCH
+  MIC_LAUNCH_CHECK();
+  return MIC_OK;
+}
+
+// The forced branch of row_lse_topk_kernel with the token read per row (gen:412-419 when the rows of one launch belong to calls with
+// different forced-BOS ids: generate() with a sequence of language ids).  No logits are read: the kernel returns from that branch.
+extern "C" int mic_row_forced_topk(int R, int k, const int32_t* forced_rows, const float* row_bias, float* top_val, int32_t* top_idx,
+                                   void* stream) {
+  MIC_CHECK(R > 0 && k >= 1 && k <= TOPK_WIDE && forced_rows && top_val && top_idx, "mic_row_forced_topk: bad args (k <= 64)");
+  hipLaunchKernelGGL((row_lse_topk_kernel<float, TOPK_WIDE>), dim3(R), dim3(256), 0, (hipStream_t)stream, 0, (const float*)nullptr, 0, k, -1, 0, 0, 0,
+                     row_bias, top_val, top_idx, forced_rows);
   MIC_LAUNCH_CHECK();
   return MIC_OK;
 }
@@ -400,13 +420,17 @@ extern "C" int mic_row_topk_tiles(int dtype, int R, int V, const void* logits, i
 // ------------------------------------------------------------------ one beam_search_body_fn iteration (gen:857-966)
 // One block per batch item, the (beam, candidate) pairs over its threads: 128 threads up to K = 8 beams (2K*K <= 128 candidates), 512
 // beyond (one pair per thread up to K = 16, four at K = 32).  All arithmetic is fp32 in the reference's operation order so scores are bit-identical to the oracle.
+// The items may belong to gridDim.y independent searches (generate() with a sequence of language ids: item i = image * groups + g is
+// item `image` of search g = i % groups; grid = (B / groups, groups), so no block divides; one search: grid = (B, 1)).  A search has
+// its own loop state gs[8] and its own stop test (gen:798-820) over its B / groups items.
 __global__ __launch_bounds__(512) void beam_step_kernel(mic_beam_step_args a) {
   extern __shared__ int32_t lds_i[];
   const int K = a.K, C = 2 * K, L = a.max_len, V = a.V;
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int b = blockIdx.x * gridDim.y + blockIdx.y, tid = threadIdx.x;
+  const int grp = blockIdx.y;
   // loop state on the device (gen:798-820 evaluated by the last block of every step): once the search has ended, further
   // launches of this kernel leave the state alone, so the host may enqueue steps ahead of reading the flag
-  if (a.gstate && __hip_atomic_load(a.gstate + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+  if (a.gstate && __hip_atomic_load(a.gstate + 8 * grp + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
   int32_t* old_run = lds_i;                 // [K][L]
   int32_t* old_seq = old_run + K * L;       // [K][L]
   int32_t* old_src = old_seq + K * L;       // [K][L]
@@ -516,33 +540,41 @@ __global__ __launch_bounds__(512) void beam_step_kernel(mic_beam_step_args a) {
     a.flags[b * 2 + 0] = all_fin;
     a.flags[b * 2 + 1] = improve;
     if (a.gstate) {
-      // gstate: [0] items with every beam finished, [1] items that can still improve, [2] arrival ticket, [3] done, [4] steps taken
-      if (all_fin) atomicAdd(a.gstate + 0, 1);
-      if (improve) atomicAdd(a.gstate + 1, 1);
+      int32_t* gs = a.gstate + 8 * grp;
+      const int per = gridDim.x;  // items of one search
+      // gs: [0] items with every beam finished, [1] items that can still improve, [2] arrival ticket, [3] done, [4] steps taken
+      if (all_fin) atomicAdd(gs + 0, 1);
+      if (improve) atomicAdd(gs + 1, 1);
       __threadfence();
-      if (atomicAdd(a.gstate + 2, 1) == a.B - 1) {  // last item of this step
+      if (atomicAdd(gs + 2, 1) == per - 1) {  // last item of this search in this step
         __threadfence();
-        const int nfin = __hip_atomic_load(a.gstate + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int nimp = __hip_atomic_load(a.gstate + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int stop = (nfin == a.B && a.early_stopping) || nimp != a.B || a.cur_len + 1 >= L;
-        a.gstate[0] = 0; a.gstate[1] = 0; a.gstate[2] = 0;
-        a.gstate[4] += 1;
+        const int nfin = __hip_atomic_load(gs + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int nimp = __hip_atomic_load(gs + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int stop = (nfin == per && a.early_stopping) || nimp != per || a.cur_len + 1 >= L;
+        gs[0] = 0; gs[1] = 0; gs[2] = 0;
+        gs[4] += 1;
         __threadfence();
-        if (stop) __hip_atomic_store(a.gstate + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (stop) __hip_atomic_store(gs + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
   }
 }
-extern "C" int mic_beam_step(const mic_beam_step_args* a, void* stream) {
+static int beam_step_launch(const mic_beam_step_args* a, int groups, void* stream) {
   MIC_CHECK(a && a->B > 0 && a->K >= 1 && 2 * a->K <= TOPK_WIDE && a->max_len > 1 && a->cur_len >= 1 && a->cur_len < a->max_len,
             "mic_beam_step: bad shape (K <= 32 supported: per-row candidates come from mic_row_lse_topk with k = 2K <= 64)");
   MIC_CHECK(a->cand_val && a->cand_idx && a->running_seq && a->running_scores && a->seq && a->scores && a->finished && a->src_row && a->next_token && a->flags, "mic_beam_step: null pointer");
   const size_t lds = (size_t)(3 * a->K * a->max_len + 8 * 2 * a->K + 8 * a->K) * 4;
   MIC_CHECK(lds <= 65536, "mic_beam_step: max_len too large for the LDS staging");
   const int threads = 2 * a->K * a->K <= 128 ? 128 : 512;  // one thread per (beam, candidate) pair
-  hipLaunchKernelGGL(beam_step_kernel, dim3(a->B), dim3(threads), lds, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(beam_step_kernel, dim3(a->B / groups, groups), dim3(threads), lds, (hipStream_t)stream, *a);
   MIC_LAUNCH_CHECK();
   return MIC_OK;
+}
+extern "C" int mic_beam_step(const mic_beam_step_args* a, void* stream) { return beam_step_launch(a, 1, stream); }
+extern "C" int mic_beam_step_groups(const mic_beam_step_args* a, int groups, void* stream) {
+  MIC_CHECK(a && groups >= 1 && a->B > 0 && a->B % groups == 0, "mic_beam_step_groups: B must be a positive multiple of groups");
+  MIC_CHECK(groups <= 65535, "mic_beam_step_groups: more than 65535 groups");
+  return beam_step_launch(a, groups, stream);
 }
 
 // ------------------------------------------------------------------ greedy step (gen:499-512)

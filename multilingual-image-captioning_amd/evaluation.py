@@ -95,3 +95,20 @@ def evaluate(trainer, eval_loaders: Dict[str, Iterable[dict]], lang_code_to_id: 
             out[lang] = compute_metrics(preds, labels, batch_decode, word_tokenize)
     out["loss"] = float(np.mean(losses)) if losses else float("nan")
     return out
+
+
+def generate_languages(model, pixel_values, lang_ids: Dict[str, int], *, via: str = "forced_bos", max_length: int = 64,
+                       num_beams: int = 4) -> Dict[str, np.ndarray]:
+    """Captions of the same images in every language of `lang_ids` ({"en_XX": id, ...}) from ONE `generate` call: the language
+    ids go in as a sequence, the images are encoded once and all languages share one decode chain; the result per language is
+    that of its own call (`evaluation.py:80-94` calls generate once per language).  `via` names the argument that selects the
+    language: "forced_bos" (`forced_bos_token_id`) or "decoder_start" (`decoder_start_token_id`, main.py:820).
+    Returns {language: int32 ids [batch, max_length]}.  `evaluate()` keeps one call per language: its loaders carry different
+    images per language."""
+    arg = {"forced_bos": "forced_bos_token_id", "decoder_start": "decoder_start_token_id"}.get(via)
+    if arg is None:
+        raise ValueError(f"via={via!r}: expected 'forced_bos' or 'decoder_start'")
+    langs = list(lang_ids)
+    gen = model.generate(pixel_values, max_length=max_length, num_beams=num_beams, **{arg: [int(lang_ids[l]) for l in langs]})
+    seq = np.asarray(gen.sequences.cpu())
+    return {l: seq[g] for g, l in enumerate(langs)}

@@ -48,6 +48,60 @@ _AUTO_SLICES = 1   # MIC_DECODE_SLICES=auto
 _RETIRED_GRAPHS = []
 
 
+def _id_sequence(name: str, value):
+    """None for a scalar (or None); the list of ints for a list / tuple / 1-D integer array"""
+    import numpy as np
+
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu().numpy()
+    if isinstance(value, np.ndarray):
+        if value.ndim == 0:
+            return None
+        if value.ndim != 1 or not np.issubdtype(value.dtype, np.integer):
+            raise ValueError(f"`{name}`: a sequence of language ids must be a 1-D integer array, got shape {value.shape} dtype {value.dtype}")
+        value = value.tolist()
+    elif not isinstance(value, (list, tuple)):
+        return None
+    if len(value) == 0:
+        raise ValueError(f"`{name}`: empty sequence of language ids")
+    for v in value:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"`{name}`: language ids must be integers, got {v!r}")
+    return [int(v) for v in value]
+
+
+def normalize_language_ids(decoder_start_token_id=None, forced_bos_token_id=None):
+    """`generate()`'s language arguments -> (G, bos_ids, start_ids, grouped).
+
+    Either argument may be a scalar (or None: the config's default applies later) or a sequence of G >= 1 ints — list, tuple,
+    1-D numpy / torch integer array.  A sequence selects the grouped call (G separate searches on the same images) whatever its
+    length: the type decides.  Two sequences must have the same length; a scalar beside a sequence is broadcast.  bos_ids /
+    start_ids are lists of G ints, or None where the argument was None.  Scalars: G = 1, grouped False, one-element lists."""
+    seqs = {"decoder_start_token_id": _id_sequence("decoder_start_token_id", decoder_start_token_id),
+            "forced_bos_token_id": _id_sequence("forced_bos_token_id", forced_bos_token_id)}
+    given = [v for v in seqs.values() if v is not None]
+    if len(given) == 2 and len(given[0]) != len(given[1]):
+        raise ValueError(f"`decoder_start_token_id` lists {len(given[0])} languages, `forced_bos_token_id` {len(given[1])}")
+    if not given:  # today's scalar call: the values pass through untouched
+        return 1, (None if forced_bos_token_id is None else [forced_bos_token_id]), \
+            (None if decoder_start_token_id is None else [decoder_start_token_id]), False
+    G = len(given[0])
+    out = []
+    for name, raw in (("forced_bos_token_id", forced_bos_token_id), ("decoder_start_token_id", decoder_start_token_id)):
+        if seqs[name] is not None:
+            out.append(seqs[name])
+        elif raw is None:
+            out.append(None)
+        else:
+            try:
+                import operator
+
+                out.append([operator.index(raw.item() if hasattr(raw, "item") else raw)] * G)
+            except (TypeError, ValueError):
+                raise ValueError(f"`{name}`: expected an integer or a sequence of integers, got {raw!r}") from None
+    return G, out[0], out[1], True
+
+
 class _DecodePlan:
     """Fixed-address device state of one generate configuration + its captured decoder steps."""
 
@@ -134,15 +188,27 @@ class FlaxCLIPVisionMBartGenerationMixin:
         Limits of this build (the reference has none of the first two; the third is the reference's own): `num_beams <= 32` — the fused
         per-row top-2K kernel keeps k = 2 * num_beams <= 64 candidates per row, a wider search raises NotImplementedError (the reference's
         evaluation runs num_beams = 4, evaluation.py:80-94); `max_length <= max_position_embeddings` (XLA's gather would clamp silently,
-        this raises); beam search with sampling raises NotImplementedError as upstream (gen:336)."""
+        this raises); beam search with sampling raises NotImplementedError as upstream (gen:336).
+
+        Several languages in one call: `forced_bos_token_id` and / or `decoder_start_token_id` may be a sequence of G >= 1 ints (list,
+        tuple, 1-D numpy / torch integer array; a scalar beside a sequence is broadcast, two sequences must agree in length; a sequence of
+        length 1 still takes this path).  The result is that of G separate calls on the same images, one per entry — each with its own
+        stop test (gen:798-820 is `jnp.all` over the images of ONE call) — computed as one decode chain of G x the rows: the encoder runs
+        once, cross-attention K/V are projected once per image, decoder row = (image * G + g) * num_beams + beam.  Returns
+        `sequences [G, B, max_length]` and, for beam search, `scores [G, B]` and `out["steps"]` = a list of G step counts.  Greedy and
+        beam search only (`do_sample=True` raises NotImplementedError); the search runs unsliced (MIC_DECODE_SLICES is ignored here);
+        MIC_DECODE_GRAPHS=1 works as for a single chain."""
         mc = self.config.mbart_config
+        G, bos_ids, start_ids, grouped = normalize_language_ids(decoder_start_token_id, forced_bos_token_id)
+        if grouped:  # resolved per language below; the scalar code in between sees "not given"
+            decoder_start_token_id = forced_bos_token_id = None
         from_processed = bool(model_kwargs.pop("sample_from_processed_logits", False))  # build-only switch, see _sample
         max_length = max_length if max_length is not None else mc.max_length  # gen:205-209
         bos_token_id = bos_token_id if bos_token_id is not None else mc.bos_token_id
         pad_token_id = pad_token_id if pad_token_id is not None else mc.pad_token_id
         eos_token_id = eos_token_id if eos_token_id is not None else mc.eos_token_id
         decoder_start_token_id = decoder_start_token_id if decoder_start_token_id else mc.decoder_start_token_id  # gen:225-229
-        if decoder_start_token_id is None and self.config.is_encoder_decoder:
+        if decoder_start_token_id is None and self.config.is_encoder_decoder and not (grouped and start_ids is not None and all(start_ids)):
             raise ValueError("`decoder_start_token_id` has to be defined for encoder-decoder generation.")  # gen:232-235
         do_sample = do_sample if do_sample is not None else mc.do_sample
         num_beams = num_beams if num_beams is not None else mc.num_beams
@@ -151,6 +217,17 @@ class FlaxCLIPVisionMBartGenerationMixin:
         if max_length > mc.max_position_embeddings:
             # the learned position table has max_position_embeddings (+2 offset) rows; XLA's gather would clamp silently
             raise ValueError(f"max_length={max_length} exceeds mbart_config.max_position_embeddings={mc.max_position_embeddings}")
+        lang = None
+        if grouped:
+            if do_sample:
+                raise NotImplementedError("do_sample=True with a sequence of language ids is not implemented: several languages per call "
+                                          "are served by greedy and beam search only")
+            if bos_ids is None and mc.forced_bos_token_id is not None:
+                bos_ids = [mc.forced_bos_token_id] * G
+            lang = dict(G=G, start=[s if s else decoder_start_token_id for s in (start_ids or [None] * G)], bos=bos_ids)  # gen:225-229 per language
+            for ids in (lang["start"], lang["bos"] or []):  # these index the embedding table on the device
+                if any(not 0 <= v < mc.vocab_size for v in ids):
+                    raise ValueError(f"language ids {ids} outside the vocabulary [0, {mc.vocab_size})")
         # gen:109-120: `params=` is NOT forwarded to encode (the encoder always uses self.params); the decoder uses it.
         enc = self.encode(input_ids, return_dict=True, **{k: v for k, v in model_kwargs.items()
                                                           if not (k.startswith("decoder_") or k.startswith("cross_attn"))})
@@ -162,9 +239,9 @@ class FlaxCLIPVisionMBartGenerationMixin:
         forced_bos_token_id = forced_bos_token_id if forced_bos_token_id is not None else mc.forced_bos_token_id
         forced_eos_token_id = forced_eos_token_id if forced_eos_token_id is not None else mc.forced_eos_token_id
         procs = dict(min_length=min_length if (min_length is not None and eos_token_id is not None and min_length > -1) else None,
-                     forced_bos=forced_bos_token_id, forced_eos=forced_eos_token_id)
+                     forced_bos=None if lang else forced_bos_token_id, forced_eos=forced_eos_token_id)  # (per-row BOS ids travel in `lang`)
         if not do_sample and num_beams == 1:
-            return self._greedy_search(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, procs)
+            return self._greedy_search(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, procs, lang)
         elif do_sample and num_beams == 1:
             mcfg = mc
             top_k = top_k if top_k is not None else getattr(mcfg, "top_k", 50)  # gen:349-356
@@ -177,7 +254,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
             length_penalty = length_penalty if length_penalty is not None else mc.length_penalty  # gen:733-742
             early_stopping = early_stopping if early_stopping is not None else mc.early_stopping
             return self._beam_search(ehs, B, num_beams, decoder_start_token_id, max_length, pad_token_id, eos_token_id,
-                                     length_penalty, early_stopping, procs)
+                                     length_penalty, early_stopping, procs, lang)
         else:
             raise NotImplementedError("`Beam sampling is currently not implemented.")  # gen:336
 
@@ -223,10 +300,20 @@ class FlaxCLIPVisionMBartGenerationMixin:
         return {"k": [plan.t[f"k{l}"] for l in range(L)], "v": [plan.t[f"v{l}"] for l in range(L)], "cache_index": 0,
                 "max_length": max_length, "rows": rows, "src_row": None, "cross": None, "row_div": 1}
 
-    def _greedy_search(self, ehs, B, start_token, max_length, pad_token_id, eos_token_id, procs):
+    def _lang_rows(self, t, ids, images: int, beams: int, name: str):
+        """plan tensor t[name] ([images * G * beams] int32) := ids[g] for row (image * G + g) * beams + beam: one small host-to-device
+        copy and a broadcasting device copy"""
+        G = len(ids)
+        t[name].view(images, G, beams).copy_(torch.tensor(ids, dtype=torch.int32).to(self.device).view(1, G, 1).expand(images, G, beams))
+        return t[name]
+
+    def _greedy_search(self, ehs, B, start_token, max_length, pad_token_id, eos_token_id, procs, lang=None):
+        """lang = None: B rows.  lang = dict(G, start, bos): G searches per image, row = image * G + g (n_img images below)"""
         from .modeling_clip_vision_mbart import ModelOutput
 
         dev, st = self.device, self.store
+        G = lang["G"] if lang else 1
+        n_img, B = B, B * G
 
         def build(plan):
             t = plan.t
@@ -236,18 +323,28 @@ class FlaxCLIPVisionMBartGenerationMixin:
             t["top_val"] = torch.empty((B, 1), dtype=torch.float32, device=dev)
             t["top_idx"] = torch.empty((B, 1), dtype=torch.int32, device=dev)
             t["pos_all"] = torch.arange(max_length, dtype=torch.int32, device=dev).repeat_interleave(B)
+            if lang:
+                t["start_rows"] = torch.empty(B, dtype=torch.int32, device=dev)
+                t["bos_rows"] = torch.empty(B, dtype=torch.int32, device=dev)
 
-        plan = self._decode_plan(("greedy", B, max_length, pad_token_id, eos_token_id, procs["min_length"], procs["forced_eos"], self.dtype),
-                                 build)
+        plan = self._decode_plan(("greedy", B, max_length, pad_token_id, eos_token_id, procs["min_length"], procs["forced_eos"], self.dtype)
+                                 + ((("G", G),) if lang else ()), build)
         t = plan.t
         sequences, finished, next_token, top_val, top_idx, pos_all = (t[k] for k in ("sequences", "finished", "next_token", "top_val",
                                                                                      "top_idx", "pos_all"))
         sequences.fill_(pad_token_id)  # gen:457
-        sequences[:, 0].fill_(start_token)  # (a fill kernel: assigning a Python scalar into a device tensor is a synchronous copy)
         finished.zero_()
-        next_token.fill_(start_token)
+        bos_rows = None
+        if lang:
+            next_token.copy_(self._lang_rows(t, lang["start"], n_img, 1, "start_rows"))
+            sequences[:, 0].copy_(next_token)
+            if lang["bos"] is not None:
+                bos_rows = self._lang_rows(t, lang["bos"], n_img, 1, "bos_rows")
+        else:
+            sequences[:, 0].fill_(start_token)  # (a fill kernel: assigning a Python scalar into a device tensor is a synchronous copy)
+            next_token.fill_(start_token)
         cache = self._plan_cache(plan, B, max_length)
-        self._decode_set_encoder(cache, ehs.reshape(B * st.S, st.d), B, 1)
+        self._decode_set_encoder(cache, ehs.reshape(n_img * st.S, st.d), n_img, G)
         use_graphs = _graphs_enabled(dev)
 
         def step(cur_len):
@@ -256,8 +353,11 @@ class FlaxCLIPVisionMBartGenerationMixin:
                     cache["cache_index"] = cur_len - 1
                     logits = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * B: cur_len * B])
                     forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
-                    ops.row_lse_topk(logits, logits.stride(0), st.V, 1, top_val, top_idx, B, forced_token=forced, suppress_eos=suppress,
-                                     eos_token_id=eos_token_id, raw_logits=True)
+                    if bos_rows is not None and cur_len == 1 and forced < 0:  # ForcedBOS per language (a ForcedEOS at max_length == 2 wins)
+                        ops.row_forced_topk(B, 1, bos_rows, top_val, top_idx)
+                    else:
+                        ops.row_lse_topk(logits, logits.stride(0), st.V, 1, top_val, top_idx, B, forced_token=forced, suppress_eos=suppress,
+                                         eos_token_id=eos_token_id, raw_logits=True)
                     ops.greedy_step(B, max_length, cur_len, eos_token_id, pad_token_id, top_idx, 1, sequences, finished, next_token)
             return fn
 
@@ -270,6 +370,8 @@ class FlaxCLIPVisionMBartGenerationMixin:
             plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)  # step 1 carries the call's forced-BOS id: never captured
             cur_len += 1
         plan.calls += 1
+        if lang:
+            return ModelOutput(sequences=sequences.view(n_img, G, max_length).transpose(0, 1).contiguous())
         return ModelOutput(sequences=sequences.clone())
 
     # ------------------------------------------------------------------ gen:537-663
@@ -335,14 +437,19 @@ class FlaxCLIPVisionMBartGenerationMixin:
             n -= 1
         return max(n, 1)
 
-    def _beam_search(self, ehs, B, K, start_token, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs):
+    def _beam_search(self, ehs, B, K, start_token, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, lang=None):
+        """lang = None: one search over B images.  lang = dict(G, start, bos): G searches over the same n_img images in one unsliced
+        chain — bookkeeping item i = image * G + g belongs to search g (mic_beam_step_groups), its K rows share the image's cross K/V
+        with the rows of the other searches (row_div = G * K)."""
         from .modeling_clip_vision_mbart import ModelOutput
 
         if 2 * K > 64:
             raise NotImplementedError("num_beams > 32 needs a wider per-row top-k than this build ships (k = 2*num_beams <= 64)")
         dev, st = self.device, self.store
-        NS = self._decode_slices(B, K)
-        Bs = B // NS          # images per slice
+        G = lang["G"] if lang else 1
+        n_img, B = B, B * G   # B: bookkeeping items
+        NS = 1 if lang else self._decode_slices(B, K)
+        Bs = B // NS          # items per slice
         R = Bs * K            # decoder rows per slice
 
         def build_slice(sub):
@@ -358,7 +465,10 @@ class FlaxCLIPVisionMBartGenerationMixin:
             t["cand_val"] = torch.empty((R, 2 * K), dtype=torch.float32, device=dev)
             t["cand_idx"] = torch.empty((R, 2 * K), dtype=torch.int32, device=dev)
             t["pos_all"] = torch.arange(max_length, dtype=torch.int32, device=dev).repeat_interleave(R)  # position ids of every step
-            t["gstate"] = torch.empty(8, dtype=torch.int32, device=dev)
+            t["gstate"] = torch.empty((G, 8) if lang else 8, dtype=torch.int32, device=dev)
+            if lang:
+                t["start_rows"] = torch.empty(R, dtype=torch.int32, device=dev)
+                t["bos_rows"] = torch.empty(R, dtype=torch.int32, device=dev)
             t["score0"] = torch.tensor([0.0] + [NEG] * (K - 1), dtype=torch.float32, device=dev).repeat(Bs, 1).contiguous()
             t["rows"] = torch.arange(R, dtype=torch.int32, device=dev)
 
@@ -369,18 +479,25 @@ class FlaxCLIPVisionMBartGenerationMixin:
             plan.streams = [torch.cuda.Stream(device=dev) for _ in range(NS)] if NS > 1 else []
 
         plan = self._decode_plan(("beam", B, K, NS, max_length, pad_token_id, eos_token_id, float(length_penalty), bool(early_stopping),
-                                  procs["min_length"], procs["forced_eos"], self.dtype), build)
-        ehs = ehs.reshape(B, st.S * st.d)
+                                  procs["min_length"], procs["forced_eos"], self.dtype) + ((("G", G),) if lang else ()), build)
+        ehs = ehs.reshape(n_img, st.S * st.d)
         steps_fn = []
         for i, sub in enumerate(plan.subs):
             t = sub.t
             t["running_seq"].fill_(pad_token_id)  # gen:751-757
-            t["running_seq"][:, :, 0].fill_(start_token)
+            bos_rows = None
+            if lang:
+                t["next_token"].copy_(self._lang_rows(t, lang["start"], n_img, K, "start_rows"))
+                t["running_seq"][:, :, 0].copy_(t["next_token"].view(Bs, K))
+                if lang["bos"] is not None:
+                    bos_rows = self._lang_rows(t, lang["bos"], n_img, K, "bos_rows")
+            else:
+                t["running_seq"][:, :, 0].fill_(start_token)
+                t["next_token"].fill_(start_token)
             t["seq"].fill_(pad_token_id)
             t["finished"].zero_()  # gen:760
             t["running_scores"].copy_(t["score0"])  # gen:763-765
             t["scores"].fill_(NEG)  # gen:766
-            t["next_token"].fill_(start_token)
             t["src_row"].zero_()
             t["src_row"][:, 0] = t["rows"]
             t["flags"].zero_()
@@ -388,12 +505,16 @@ class FlaxCLIPVisionMBartGenerationMixin:
             cache["src_row"] = t["src_row"]
             cache["ns"] = f"s{i}." if NS > 1 else ""
             # encoder states are shared by an image's K beams (gen:299-307 broadcasts them; here: row r reads image r // K)
-            self._decode_set_encoder(cache, ehs[i * Bs:(i + 1) * Bs].reshape(Bs * st.S, st.d), Bs, K)
+            if lang:
+                self._decode_set_encoder(cache, ehs.reshape(n_img * st.S, st.d), n_img, G * K)
+            else:
+                self._decode_set_encoder(cache, ehs[i * Bs:(i + 1) * Bs].reshape(Bs * st.S, st.d), Bs, K)
             # beam_search_cond_fn (gen:798-820) lives on the device: mic_beam_step evaluates it on the new state, and once it says
             # stop every later mic_beam_step launch is a no-op.  The host therefore enqueues decoder steps (graph replays once the
             # plan is warm) without waiting and looks at the flag only every _POLL steps.
             t["gstate"].zero_()
-            steps_fn.append(self._beam_step_fn(cache, t, Bs, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs))
+            steps_fn.append(self._beam_step_fn(cache, t, Bs, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs,
+                                               groups=G if lang else None, bos_rows=bos_rows))
         use_graphs = _graphs_enabled(dev, NS)
 
         def step(cur_len):
@@ -416,6 +537,25 @@ class FlaxCLIPVisionMBartGenerationMixin:
             return fn
 
         gstates = [sub.t["gstate"] for sub in plan.subs]
+        if lang:
+            # one [G, 8] tensor: a search that has stopped leaves its state alone while its rows ride along (its outputs are those of
+            # the separate call that stopped there); the loop ends when every search has stopped
+            gs = gstates[0]
+            cur_len = 1
+            while cur_len < max_length:
+                plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)
+                cur_len += 1
+                if cur_len < max_length and (cur_len - 1) % _POLL == 0 and bool((gs[:, 3] != 0).all().item()):
+                    break
+            plan.calls += 1
+            t = plan.subs[0].t
+            any_fin = t["finished"].bool().any(dim=1)  # gen:980-990, as below
+            out_seq = torch.where(any_fin[:, None, None], t["seq"], t["running_seq"])[:, -1]
+            out_scores = torch.where(any_fin[:, None], t["scores"], t["running_scores"])[:, -1]
+            out = ModelOutput(sequences=out_seq.view(n_img, G, max_length).transpose(0, 1).contiguous(),
+                              scores=out_scores.view(n_img, G).transpose(0, 1).contiguous())
+            out["steps"] = [int(v) for v in gs[:, 4].tolist()]
+            return out
         cur_len = 1
         while cur_len < max_length:
             plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)  # step 1 carries the call's forced-BOS id: never captured
@@ -435,8 +575,10 @@ class FlaxCLIPVisionMBartGenerationMixin:
         out["steps"] = steps
         return out
 
-    def _beam_step_fn(self, cache, t, B, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs):
-        """the launches of one beam-search step (gen:822-966) of one slice of B images: step(cur_len)"""
+    def _beam_step_fn(self, cache, t, B, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, groups=None,
+                      bos_rows=None):
+        """the launches of one beam-search step (gen:822-966) of one slice of B items: step(cur_len).  groups = G: the items belong to G
+        searches (item i to search i % G, gstate [G][8]); bos_rows: per-row ForcedBOS ids of such a call"""
         st = self.store
         R = B * K
         running_seq, seq, finished, running_scores, scores = t["running_seq"], t["seq"], t["finished"], t["running_scores"], t["scores"]
@@ -448,7 +590,9 @@ class FlaxCLIPVisionMBartGenerationMixin:
                 cache["cache_index"] = cur_len - 1
                 logits, stat = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R], stats=True)  # gen:830-840
                 forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
-                if stat is not None and forced < 0 and 2 * K <= 16:
+                if bos_rows is not None and cur_len == 1 and forced < 0:  # ForcedBOS per language (a ForcedEOS at max_length == 2 wins)
+                    ops.row_forced_topk(R, 2 * K, bos_rows, cand_val, cand_idx, row_bias=running_scores.reshape(-1))
+                elif stat is not None and forced < 0 and 2 * K <= 16:
                     # log-softmax + top-2K from the head GEMM's per-granule partials: 3908 pairs and a few 64-column granules
                     # per row instead of two passes over the 250 054 logits (same candidates, same order, same fp32 arithmetic)
                     ops.row_topk_tiles(logits, logits.stride(0), st.V, stat, 2 * K, cand_val, cand_idx, R, suppress_eos=suppress,
@@ -457,5 +601,6 @@ class FlaxCLIPVisionMBartGenerationMixin:
                     ops.row_lse_topk(logits, logits.stride(0), st.V, 2 * K, cand_val, cand_idx, R, forced_token=forced,
                                      suppress_eos=suppress, eos_token_id=eos_token_id, row_bias=running_scores.reshape(-1))  # gen:850-873
                 ops.beam_step(B, K, max_length, st.V, cur_len, eos_token_id, pad_token_id, length_penalty, early_stopping, cand_val,
-                              cand_idx, running_seq, running_scores, seq, scores, finished, src_row, next_token, flags, gstate=gstate)  # gen:872-966
+                              cand_idx, running_seq, running_scores, seq, scores, finished, src_row, next_token, flags, gstate=gstate,
+                              groups=groups)  # gen:872-966
         return step

@@ -491,8 +491,14 @@ def row_lse_topk(logits, ld, V, k, top_val, top_idx, R, *, forced_token=-1, supp
                                      int(raw_logits), _p(row_bias), _p(top_val), _p(top_idx), _stream()), "mic_row_lse_topk")
 
 
+def row_forced_topk(R, k, forced_rows, top_val, top_idx, *, row_bias=None):
+    """row_lse_topk's forced-token result with the token of row r read from forced_rows[r] (int32)"""
+    L.check(L.lib().mic_row_forced_topk(R, k, _p(forced_rows), _p(row_bias), _p(top_val), _p(top_idx), _stream()), "mic_row_forced_topk")
+
+
 def beam_step(B, K, max_len, V, cur_len, eos, pad, length_penalty, early_stopping, cand_val, cand_idx, running_seq, running_scores,
-              seq, scores, finished, src_row, next_token, flags, gstate=None):
+              seq, scores, finished, src_row, next_token, flags, gstate=None, groups=None):
+    """groups = None: mic_beam_step.  groups = G: mic_beam_step_groups — item i belongs to search i % G, gstate is [G][8]."""
     a = L.BeamStepArgs()
     a.B, a.K, a.max_len, a.V, a.cur_len = B, K, max_len, V, cur_len
     a.eos_token_id, a.pad_token_id, a.length_penalty, a.early_stopping = eos, pad, float(length_penalty), int(bool(early_stopping))
@@ -500,7 +506,10 @@ def beam_step(B, K, max_len, V, cur_len, eos, pad, length_penalty, early_stoppin
     a.running_seq, a.running_scores, a.seq, a.scores = _p(running_seq), _p(running_scores), _p(seq), _p(scores)
     a.finished, a.src_row, a.next_token, a.flags = _p(finished), _p(src_row), _p(next_token), _p(flags)
     a.gstate = _p(gstate)
-    L.check(L.lib().mic_beam_step(C.byref(a), _stream()), "mic_beam_step")
+    if groups is None:
+        L.check(L.lib().mic_beam_step(C.byref(a), _stream()), "mic_beam_step")
+    else:
+        L.check(L.lib().mic_beam_step_groups(C.byref(a), int(groups), _stream()), "mic_beam_step_groups")
 
 
 def greedy_step(B, max_len, cur_len, eos, pad, top_idx, ld_top, sequences, finished, next_token):
