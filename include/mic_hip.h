@@ -219,7 +219,9 @@ typedef struct {
 
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm (flax nn.LayerNorm: biased variance, fp32 statistics; 3P).
- *   fwd: y = (x-mean)*rstd*gamma + beta, then optional dropout; saves mean/rstd [rows] (may be NULL).
+ *   fwd: y = (x-mean)*rstd*gamma + beta, then optional dropout; saves mean/rstd [rows] (may be NULL — in forward only: the
+ *        backward entry points refuse a NULL mean or rstd).  A dropped element is an exact zero, a kept one y / (1-p).
+ *        width % 8 == 0, width <= 2048; rows are contiguous (stride = width), 16-B aligned.
  *   bwd: dx = LNbwd(dy) (+ dres if given);  dgamma/dbeta accumulated with fp32 atomics (caller zeroes);
  *        optional second output dxm = dropout_mask(seed_m) * dx / (1-p_m): the gradient entering the
  *        residual branch that produced x (its epilogue applied that dropout in forward).
@@ -232,7 +234,8 @@ int mic_layernorm_bwd(int dtype, int rows, int width, const void* x, const float
                       void* dxm, float dropout_p, uint32_t dropout_seed, float in_dropout_p, uint32_t in_dropout_seed,
                       void* stream);
 /* mic_layernorm_bwd with the gamma / beta gradients as per-block partial column sums (plain stores) instead of fp32 atomics:
- * partials [2][mic_layernorm_bwd_blocks(rows)][width] fp32 (gamma sums first), fully overwritten.  mic_ln_param_grads adds the blocks
+ * partials [2][mic_layernorm_bwd_blocks(rows)][width] fp32 (gamma sums first), fully overwritten (every entry, nothing
+ * outside it; a NULL `partials` is refused).  mic_ln_param_grads adds the blocks
  * up in block order — deterministic, and off the critical path: the atomics were a third of the kernel's time at 2.4 k rows. */
 int mic_layernorm_bwd_blocks(int rows);
 int mic_layernorm_bwd_partials(int dtype, int rows, int width, const void* x, const float* gamma, const float* mean,
@@ -349,6 +352,14 @@ int64_t mic_embed_rows_add_det_ws(int vocab);
  *   logits [rows][ld] (dtype), columns >= V are padding.  Pass 1 (mic_ce_rows): per-row lse, nll(ls) -> row_loss,
  *   Pass 2 (mic_ce_bwd): logits <- dlogits = mask/denom * (softmax - soft_label) in place, padding columns <- 0,
  *   where denom = sum(mask) is read from device (denom[0]).  loss = sum(row_loss*mask)/denom by mic_ce_reduce.
+ *   Logits may be -inf (a suppressed token) as long as a row keeps one finite entry: row_lse is the finite log-sum-exp of the rest
+ *   (a chunk or a whole 64-column granule of -inf included), the gradient at such an entry is w (0 - low); with label smoothing the
+ *   row's loss is then +inf, as the formula says.
+ *   Exact zeros (+0 bits) of mic_ce_bwd / mic_ce_bwd_t: the padding columns V .. Vpad of every row (whatever they held, NaN
+ *   included) and every entry of a row whose mask is 0; columns Vpad .. ld are not written.  mic_ce_reduce: denom is the exact
+ *   count, a row of mask 0 contributes nothing (its row_loss must be finite).
+ *   labels must lie in [0, V) on EVERY row of mic_ce_rows / mic_ce_rows_tiles, masked rows included: logits[label] is read
+ *   unconditionally (mic_ce_rows does not read `mask`).  V > 1, ld >= V (mic_ce_rows: ld % 8 == 0), Vpad % 8 == 0, ld >= Vpad.
  * ------------------------------------------------------------------------------------------- */
 int mic_ce_rows(int dtype, int rows, int V, const void* logits, int ld, const int32_t* labels,
                 const int32_t* mask, float label_smoothing, float* row_lse, float* row_loss, void* stream);

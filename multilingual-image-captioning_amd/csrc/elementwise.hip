@@ -418,10 +418,13 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(int V, const T* __restrict
 #pragma unroll
     for (int i = 0; i < 8; ++i) if (ch * 8 + i < V) cm = fmaxf(cm, v[i]);
     const float mn = fmaxf(m, cm);
+    // a chunk of -inf under a running maximum of -inf: exp(-inf - -inf) is NaN — rescale against 0 instead (every term is then
+    // exp(-inf) = 0 and s stays 0), as online_merge and ce_rows_tiles_kernel do
+    const float base = mn == -INFINITY ? 0.f : mn;
     float add = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) if (ch * 8 + i < V) { add += __expf(v[i] - mn); tot += v[i]; }
-    s = s * __expf(m - mn) + add;
+    for (int i = 0; i < 8; ++i) if (ch * 8 + i < V) { add += __expf(v[i] - base); tot += v[i]; }
+    s = s * __expf(m - base) + add;
     m = mn;
   }
   sm[tid] = m; ss[tid] = s; st[tid] = tot;
@@ -551,7 +554,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(int V, int Vpad, T* __restr
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int c = ch * 8 + i;
-        o[i] = c < V ? w * (__expf(v[u][i] - lse) - (c == label ? conf : low)) : 0.f;
+        o[i] = c < V && w != 0.f ? w * (__expf(v[u][i] - lse) - (c == label ? conf : low)) : 0.f;  // (a masked row: +0, not 0 * negative = -0)
       }
       st8(lr + ch * 8, o);
     }
@@ -619,7 +622,7 @@ __global__ __launch_bounds__(256) void tile_transpose_kernel(TransposeArgs a) {
         for (int i = 0; i < 8; ++i) {
           const float x = __uint_as_float((i & 1) ? (wd[i >> 1] & 0xffff0000u) : (wd[i >> 1] << 16));
           const int c = col + i;
-          o[i] = c < a.V ? w * (__expf(x - lse) - (c == label ? conf : low)) : 0.f;
+          o[i] = c < a.V && w != 0.f ? w * (__expf(x - lse) - (c == label ? conf : low)) : 0.f;
         }
         u.x = f2bf_pk(o[0], o[1]); u.y = f2bf_pk(o[2], o[3]); u.z = f2bf_pk(o[4], o[5]); u.w = f2bf_pk(o[6], o[7]);
         *reinterpret_cast<uint4*>(a.src_rw + (size_t)row * a.ld_src + col) = u;
