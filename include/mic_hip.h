@@ -459,6 +459,21 @@ int mic_adamw(int64_t n, float* p, float* m, float* v, const float* g, void* p_l
 int mic_adamw_rows(int64_t rows, int width, const uint8_t* row_flag, int want, float* p, float* m, float* v, const float* g,
                    void* p_lp, const float* hyper, double b1, double b2, double eps, double wd, float grad_scale, void* stream);
 int mic_row_flags(const int32_t* ids, int n_ids, uint8_t* flags, int n_rows, void* stream);
+/* Gradient accumulation: N micro-batches per AdamW step.  The reference takes `lax.pmean(grad)` over its devices and then ONE
+ * optimizer step (main.py:698-701); the gradients of N micro-batches summed, scaled by 1/N and applied once are that step of an
+ * N-device run on one device.
+ * mic_grad_accumulate: dst[0..n) = src (init != 0) or dst + src (init == 0), one IEEE fp32 add per element; n % 4 == 0, both
+ *   pointers 16-byte aligned.  The caller picks the direction: acc += g on every micro-step but the last, g += acc in front of the
+ *   all-reduce of the last one when there are several ranks.
+ * mic_adamw_acc / mic_adamw_rows_acc: mic_adamw / mic_adamw_rows on g' = fp32(g + acc) — the sum is rounded to fp32 before
+ *   grad_scale is applied, so p, m, v and p_lp are bit for bit those of the plain entry points on a gradient summed beforehand, without
+ *   the separate pass over the buffer that sum would cost. */
+int mic_grad_accumulate(int64_t n, float* dst, const float* src, int init, void* stream);
+int mic_adamw_acc(int64_t n, float* p, float* m, float* v, const float* g, const float* acc, void* p_lp, const float* hyper, double b1,
+                  double b2, double eps, double wd, float grad_scale, void* stream);
+int mic_adamw_rows_acc(int64_t rows, int width, const uint8_t* row_flag, int want, float* p, float* m, float* v, const float* g,
+                       const float* acc, void* p_lp, const float* hyper, double b1, double b2, double eps, double wd, float grad_scale,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Generation epilogues

@@ -141,6 +141,9 @@ _SIGS = {
     "mic_adamw": ([_i64, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _f, _p], C.c_int),
     "mic_adamw_rows": ([_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _f, _p], C.c_int),
     "mic_row_flags": ([_p, _i, _p, _i, _p], C.c_int),
+    "mic_grad_accumulate": ([_i64, _p, _p, _i, _p], C.c_int),
+    "mic_adamw_acc": ([_i64, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _f, _p], C.c_int),
+    "mic_adamw_rows_acc": ([_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _f, _p], C.c_int),
     "mic_row_lse_topk": ([_i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p], C.c_int),
     "mic_beam_step": ([C.POINTER(BeamStepArgs), _p], C.c_int),
     "mic_row_forced_topk": ([_i, _i, _p, _p, _p, _p, _p], C.c_int),

@@ -468,16 +468,32 @@ def copy_rows(src, dst, n, width, *, src_idx=None, dst_idx=None):
             "mic_copy_rows")
 
 
-def adamw(p, m, v, g, p_lp, hyper, b1, b2, eps, wd, grad_scale=1.0, n=None):
+def adamw(p, m, v, g, p_lp, hyper, b1, b2, eps, wd, grad_scale=1.0, n=None, acc=None):
+    """acc (fp32, same length): the update reads g + acc (mic_adamw_acc) — the last micro-step of a gradient accumulation"""
     n = n if n is not None else p.numel()
+    if acc is not None:
+        L.check(L.lib().mic_adamw_acc(n, _p(p), _p(m), _p(v), _p(g), _p(acc), _p(p_lp), _p(hyper), float(b1), float(b2), float(eps), float(wd),
+                                      float(grad_scale), _stream()), "mic_adamw_acc")
+        return
     L.check(L.lib().mic_adamw(n, _p(p), _p(m), _p(v), _p(g), _p(p_lp), _p(hyper), float(b1), float(b2), float(eps), float(wd),
                               float(grad_scale), _stream()), "mic_adamw")
 
 
-def adamw_rows(rows, width, row_flag, want, p, m, v, g, p_lp, hyper, b1, b2, eps, wd, grad_scale=1.0):
-    """AdamW on the rows of a [rows][width] slice whose flag equals `want` (mic_adamw_rows)."""
+def adamw_rows(rows, width, row_flag, want, p, m, v, g, p_lp, hyper, b1, b2, eps, wd, grad_scale=1.0, acc=None):
+    """AdamW on the rows of a [rows][width] slice whose flag equals `want` (mic_adamw_rows; acc: on g + acc, mic_adamw_rows_acc)."""
+    if acc is not None:
+        L.check(L.lib().mic_adamw_rows_acc(int(rows), int(width), _p(row_flag), int(want), _p(p), _p(m), _p(v), _p(g), _p(acc), _p(p_lp),
+                                           _p(hyper), float(b1), float(b2), float(eps), float(wd), float(grad_scale), _stream()),
+                "mic_adamw_rows_acc")
+        return
     L.check(L.lib().mic_adamw_rows(int(rows), int(width), _p(row_flag), int(want), _p(p), _p(m), _p(v), _p(g), _p(p_lp), _p(hyper), float(b1),
                                    float(b2), float(eps), float(wd), float(grad_scale), _stream()), "mic_adamw_rows")
+
+
+def grad_accumulate(dst, src, init=False, n=None):
+    """dst = src (init) or dst += src over n fp32 elements (default: all of dst; n % 4 == 0) — mic_grad_accumulate"""
+    n = n if n is not None else dst.numel()
+    L.check(L.lib().mic_grad_accumulate(int(n), _p(dst), _p(src), int(bool(init)), _stream()), "mic_grad_accumulate")
 
 
 def row_flags(ids, n_ids, flags):

@@ -135,13 +135,14 @@ class ParamStore:
         self.numel = _rup(off, 256)
         if not allocate:
             self.master = self.lp = None
-            self.grad = self.m = self.v = None
+            self.grad = self.m = self.v = self.acc = None
             return
         self.master = torch.zeros(self.numel, dtype=torch.float32, device=device)
         self.lp = self.master if dtype == torch.float32 else torch.zeros(self.numel, dtype=dtype, device=device)
         self.grad = None
         self.m = None
         self.v = None
+        self.acc = None  # running gradient sum of a gradient accumulation (ensure_grad_acc)
 
     # ------------------------------------------------------------------ views
     def _view(self, kind: str, buf: torch.Tensor, name: str) -> torch.Tensor:
@@ -191,6 +192,11 @@ class ParamStore:
         if self.m is None:
             self.m = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
             self.v = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+
+    def ensure_grad_acc(self):
+        """flat fp32 buffer of `numel` holding the gradient sum of the micro-steps taken so far (Trainer(accumulate_steps > 1) only)"""
+        if self.acc is None:
+            self.acc = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
 
     def refresh_lp(self):
         self.version = getattr(self, "version", 0) + 1  # anything derived from the weights (folded / quantised copies) is stale
@@ -276,7 +282,7 @@ class ParamStore:
         return m
 
     def _buffer(self, which: str) -> torch.Tensor:
-        buf = {"master": self.master, "grad": self.grad, "m": self.m, "v": self.v}[which]
+        buf = {"master": self.master, "grad": self.grad, "m": self.m, "v": self.v, "acc": self.acc}[which]
         if buf is None:
             raise ValueError(f"ParamStore: the '{which}' buffer has not been allocated")
         return buf
@@ -308,7 +314,7 @@ class ParamStore:
             self.refresh_lp()
 
     def export_flat(self, source: str = "master") -> Dict[str, np.ndarray]:
-        """device buffers -> {'/'-joined flax leaf: np.ndarray} in the reference layout (source: master | grad | m | v)."""
+        """device buffers -> {'/'-joined flax leaf: np.ndarray} in the reference layout (source: master | grad | m | v | acc)."""
         out: Dict[str, np.ndarray] = {}
         shapes = self.flax_shapes()
         for seg_name, parts in self._mapping():

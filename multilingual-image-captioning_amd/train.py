@@ -232,6 +232,10 @@ class GradReducer:
       "next"       at the next progress report, behind everything backward has enqueued by then — a kernel issued right after
                    the gradient became final still READS the weights (the LM head's dX GEMM reads the tied embedding);
       "end"        in finish(), after `before()` — the gradient receives a late part (the sparse input-embedding rows).
+
+    Per step (`start_step`), for gradient accumulation: `local=True` issues no exchange at all (a micro-step whose gradient only joins
+    the running sum), `on_ready` / `ready_when` replace the callback and its ordering rule for that step, and `pre_exchange(b, e)` runs
+    on the collective stream in front of the bucket's all-reduce (the running sum joins the gradient there).
     """
 
     def __init__(self, flat_grad: torch.Tensor, buckets: List[Tuple[int, int]], group=None, on_ready=None,
@@ -276,6 +280,7 @@ class GradReducer:
             self.emulated_ms = 0.0
             self.emulated_events = []
         self.on_ready = on_ready if self.cuda else None
+        self._cb, self._when, self._local, self._pre = self.on_ready, self.ready_when, False, None  # this step's (start_step)
         self._finishing = False
         self.host_s = 0.0
         self.next = 0
@@ -319,9 +324,15 @@ class GradReducer:
 
     @property
     def active(self) -> bool:
-        return self.world > 1 or self.on_ready is not None or self.emulate is not None
+        return self.world > 1 or self._cb is not None or self.emulate is not None  # (_cb: this step's callback, see start_step)
 
-    def start_step(self):
+    def start_step(self, local: bool = False, on_ready=None, ready_when: Optional[List[str]] = None, pre_exchange=None):
+        """local: no exchange this step, whatever the world size.  on_ready / ready_when: this step's per-bucket callback and its
+        ordering rules (default: the constructor's).  pre_exchange(b, e): on the collective stream, in front of the bucket's all-reduce."""
+        self._local, self._pre = bool(local), pre_exchange
+        self._cb = on_ready if (on_ready is not None and self.cuda) else self.on_ready
+        self._when = list(ready_when) if ready_when is not None else self.ready_when
+        assert len(self._when) == len(self.buckets)
         self.host_s = 0.0
         self.next = 0
         self.handles = []
@@ -342,7 +353,7 @@ class GradReducer:
             if here is not None:
                 st.wait_event(here)
             with ops.pinned_stream():  # launch on that stream, not on the step's pinned main stream
-                self.on_ready(b, e)
+                self._cb(b, e)
 
     def _issue_pending(self):
         if not self._pending:
@@ -370,20 +381,23 @@ class GradReducer:
             self._issue_pending()
         while self.next < len(self.buckets) and self.buckets[self.next][1] <= offset_done:
             b, e = self.buckets[self.next]
-            when = self.ready_when[self.next]
+            when = self._when[self.next]
             if self.cuda:
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream())
-                if self.world > 1 or self.emulate is not None:
+                if (self.world > 1 or self.emulate is not None) and not self._local:
                     with torch.cuda.stream(self.stream):
                         self.stream.wait_event(ev)
+                        if self._pre is not None:
+                            with ops.pinned_stream():
+                                self._pre(b, e)
                         if self.world > 1:
                             self._all_reduce(b, e)
                         else:
                             self._emulated_exchange(b, e)
                         ev = torch.cuda.Event()
                         ev.record(self.stream)
-                if self.on_ready is None:
+                if self._cb is None:
                     pass
                 elif when == "end":
                     self._at_end.append((b, e))
@@ -391,7 +405,9 @@ class GradReducer:
                     self._pending.append((b, e, ev))
                 else:
                     self._issue(b, e, ev)
-            else:  # CPU tensors (host-logic tests over gloo)
+            elif not self._local:  # CPU tensors (host-logic tests over gloo)
+                if self._pre is not None:
+                    self._pre(b, e)
                 h = self._all_reduce(b, e, async_op=True)
                 if h is not None:
                     self.handles.append(h)
@@ -422,7 +438,7 @@ class GradReducer:
                 h.wait()
             return
         self._issue_pending()
-        if self.on_ready is None:
+        if self._cb is None:
             after = None  # the late pass belongs to the per-bucket optimizer
             self._at_end = []
         cur = torch.cuda.current_stream()
@@ -440,7 +456,7 @@ class GradReducer:
                     if before is not None:
                         before()
                     for (b, e) in self._at_end:
-                        self.on_ready(b, e)
+                        self._cb(b, e)
                     if after is not None:
                         after()
             if tail is not self.opt_stream:
@@ -458,14 +474,35 @@ class GradReducer:
 OPT_CUS_DEFAULT = 96  # CUs of the optimizer stream (12 per XCD of an MI355X): profiles/README.md, round 3 A/B
 
 
+def virtual_rank_dropout_seed(seed: int, rank: int, step: int, accumulate_steps: int = 1, micro_step: int = 0) -> int:
+    """Dropout seed of one forward/backward pass.  Micro-step j of rank r under `accumulate_steps=N` draws the stream of VIRTUAL rank
+    r * N + j: the per-device stream (main.py:251) of that rank, split per optimizer step (main.py:686) — so N micro-steps on one
+    GPU draw the masks N ranks would draw, and W ranks x N micro-steps those of W * N ranks.  N = 1, j = 0: what `Trainer` uses
+    without accumulation.  Pure host arithmetic."""
+    vrank = int(rank) * int(accumulate_steps) + int(micro_step)
+    stream = (int(seed) * 1000003 + vrank * 7919) & 0xFFFFFFFF
+    return (stream + int(step) * 0x9E3779B1) & 0xFFFFFFFF
+
+
 class Trainer:
-    """TrainState + train_step/eval_step of main.py, for one rank."""
+    """TrainState + train_step/eval_step of main.py, for one rank.
+
+    Gradient accumulation (`accumulate_steps=N` > 1): every `train_step(batch)` call is one MICRO-step — a forward/backward pass whose
+    gradient joins a running fp32 sum (`ParamStore.acc`) — and every N-th call is the optimizer step, on the mean of the N gradients:
+    the step an N-rank data-parallel run takes (`lax.pmean` over N devices, then one AdamW step, main.py:698-701), up to fp32
+    summation order; on W ranks that of a W * N-rank run.  `step`, the learning-rate schedule and the bias correction advance on the
+    N-th call only; the weights do not change in between.  Micro-step j of rank r draws the dropout masks of virtual rank r * N + j
+    (`virtual_rank_dropout_seed`).  The sum is kept where the optimizer is: per gradient bucket on the optimizer stream beside
+    backward (`acc += g`, 12 B/element), and on the N-th call AdamW reads `g + acc` itself.  With several ranks nothing is exchanged on
+    the first N - 1 calls; on the N-th, `g += acc` runs in front of every bucket's all-reduce.  A call that is not the N-th returns its
+    micro-batch's loss and the pending step's learning rate; the N-th returns the mean loss of the N micro-batches.  A reference
+    run at 8 devices x 64 images is `accumulate_steps=8` at a per-device batch of 64 on one GPU."""
 
     def __init__(self, model, learning_rate_fn: Callable[[int], float], b1=0.9, b2=0.999, eps=1e-8, weight_decay=0.0,
                  label_smoothing_factor=0.0, seed: int = 42, bucket_mb: float = 64.0, group=None, compact_head: bool = True,
                  overlap_optimizer: bool = True, grad_comm_dtype=None, gemm_dtype: Optional[str] = None,
                  fp8_scaling: str = "delayed", pack_rows: bool = True, comm_cus: Optional[int] = None, emulate_comm: int = 0,
-                 fp8_head: Optional[str] = None):
+                 fp8_head: Optional[str] = None, accumulate_steps: int = 1):
         """pack_rows (bfloat16 mode, with compact_head): the decoder runs on the valid caption positions only (`packed_rows`);
         exact — padded positions neither carry loss nor are attended to — and ~1/3 fewer decoder rows on ragged captions.  Needs
         prefix-shaped masks available on the host: a numpy / CPU `attention_mask`, or `batch["packed_rows"]` from the collate
@@ -479,9 +516,22 @@ class Trainer:
         `init_process_group`, or NCCL_MAX_NCHANNELS in the environment) when world > 1 — the budget then equals what RCCL was held to;
         0 (planner untouched) when no cap is in force.  A user-set MIC_FREE_CUS wins over both.
         emulate_comm = N (one GPU only; bench.py --emulate-comm): every bucket's exchange is replaced by a kernel holding
-        `comm_cus` CUs for the projected duration of its all-reduce among N ranks — a scheduling probe, not a scaling result."""
+        `comm_cus` CUs for the projected duration of its all-reduce among N ranks — a scheduling probe, not a scaling result.
+        accumulate_steps = N: micro-batches per optimizer step (class docstring).  Not combined with gemm_dtype="fp8" (the delayed
+        scales and the weight re-quantisation inside the optimizer passes assume one pass per step) or with emulate_comm."""
         import torch.distributed as dist
 
+        if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer)) or accumulate_steps < 1:
+            raise ValueError(f"accumulate_steps must be an integer >= 1, got {accumulate_steps!r}")
+        # (tools/accumulate_probe.py switches a live Trainer between N and 1 by writing `accumulate_steps` and `_gscale`: state derived
+        # from N in this constructor beyond those two — and buffers that only need to exist — has to be added to its `mode()` too)
+        self.accumulate_steps = int(accumulate_steps)
+        if self.accumulate_steps > 1 and emulate_comm:
+            raise ValueError("accumulate_steps > 1 is not supported together with emulate_comm (out of scope: the stand-in exchange "
+                             "models one pass per optimizer step)")
+        if self.accumulate_steps > 1 and (gemm_dtype == "fp8" or getattr(model.engine, "fp8", False)):
+            raise ValueError("accumulate_steps > 1 is not supported together with gemm_dtype='fp8' (out of scope: the delayed-scaling state "
+                             "and the weight re-quantisation inside the optimizer passes need their own design)")
         self.model, self.lr_fn = model, learning_rate_fn
         self.b1, self.b2, self.eps, self.wd, self.ls = b1, b2, eps, weight_decay, label_smoothing_factor
         self.compact_head = compact_head
@@ -491,6 +541,7 @@ class Trainer:
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.group = group
+        self.seed = seed
         self.dropout_seed = (seed * 1000003 + self.rank * 7919) & 0xFFFFFFFF  # per-device dropout stream (main.py:251)
         st = model.store
         st.ensure_grads()
@@ -568,6 +619,19 @@ class Trainer:
         self._det_ws = None  # workspace of the deterministic embedding-row scatter (data parallel)
         self._late_done = False
         self._late_early = _os.environ.get("MIC_LATE_EARLY", "1") != "0"  # (A/B: 0 = the flagged embedding rows' pass behind the step, as before)
+        # pmean(grad): SUM in the flat buffer, the mean folded into AdamW's grad_scale (over the ranks and, with accumulation, the micro-steps)
+        self._gscale = 1.0 / self.world
+        self._use_acc = False  # True while the optimizer passes of an accumulation's last micro-step are issued (world 1: AdamW on g + acc)
+        self._micro = 0        # micro-steps taken since the last optimizer step
+        if self.accumulate_steps > 1:
+            st.ensure_grad_acc()
+            self._gscale = 1.0 / (self.world * self.accumulate_steps)
+            # a micro-step that only accumulates: the pieces of the tied embedding wait for the input-embedding scatter at the end of
+            # decoder backward ("end"); every other bucket joins the sum as soon as backward reports it
+            self._when_acc = ["end" if (b < sh.offset + sh.numel and e > sh.offset) else "exchanged" for (b, e) in self.buckets]
+            self._acc_cb = lambda b, e: me()._accumulate_slice(b, e)
+            self._pre_cb = lambda b, e: me()._add_acc_slice(b, e)
+            self._loss_sum = None
 
     def _adamw_slice(self, b: int, e: int):
         """AdamW on flat slice [b, e) — runs on the reducer's side stream right after that bucket's all-reduce.  The part of the
@@ -578,14 +642,14 @@ class Trainer:
         lo, hi = max(b, sb), min(e, se)
         if not self._split_shared or lo >= hi:
             ops.adamw(st.master[b:e], st.m[b:e], st.v[b:e], st.grad[b:e], None if st.lp is st.master else st.lp[b:e], self.hyper,
-                      self.b1, self.b2, self.eps, self.wd, grad_scale=1.0 / self.world, n=e - b)
+                      self.b1, self.b2, self.eps, self.wd, grad_scale=self._gscale, n=e - b, acc=st.acc[b:e] if self._use_acc else None)
             self.model.engine.fp8_requantize_range(b, e)  # fp8 GEMMs: the bucket's weights as fp8 for the NEXT step, here under backward
             return
         assert (lo - sb) % width == 0 and (hi - sb) % width == 0, "bucket cuts inside the tied embedding are row-aligned"
         for (x, y) in ((b, lo), (hi, e)):
             if y > x:
                 ops.adamw(st.master[x:y], st.m[x:y], st.v[x:y], st.grad[x:y], None if st.lp is st.master else st.lp[x:y], self.hyper,
-                          self.b1, self.b2, self.eps, self.wd, grad_scale=1.0 / self.world, n=y - x)
+                          self.b1, self.b2, self.eps, self.wd, grad_scale=self._gscale, n=y - x, acc=st.acc[x:y] if self._use_acc else None)
         self._adamw_shared(0, (lo - sb) // width, (hi - sb) // width)
         self.model.engine.fp8_requantize_range(b, e)
 
@@ -597,7 +661,17 @@ class Trainer:
         x, y = sb + r0 * width, sb + r1 * width
         ops.adamw_rows(r1 - r0, width, self._row_flag[r0:r1], want, st.master[x:y], st.m[x:y], st.v[x:y], st.grad[x:y],
                        None if st.lp is st.master else st.lp[x:y], self.hyper, self.b1, self.b2, self.eps, self.wd,
-                       grad_scale=1.0 / self.world)
+                       grad_scale=self._gscale, acc=st.acc[x:y] if self._use_acc else None)
+
+    def _accumulate_slice(self, b: int, e: int):
+        """a micro-step that is not the last: acc[b:e] = grad[b:e] (first micro-step) or += (the following), on the reducer's side stream"""
+        st = self.model.store
+        ops.grad_accumulate(st.acc[b:e], st.grad[b:e], init=self._micro == 0, n=e - b)
+
+    def _add_acc_slice(self, b: int, e: int):
+        """last micro-step, several ranks: grad[b:e] += acc[b:e] on the collective stream, in front of the bucket's all-reduce"""
+        st = self.model.store
+        ops.grad_accumulate(st.grad[b:e], st.acc[b:e], init=False, n=e - b)
 
     def _adamw_shared_late(self):
         """end of backward (after the sparse embedding rows have been added): the flagged rows of the tied embedding"""
@@ -721,8 +795,10 @@ class Trainer:
 
     def train_step(self, batch: Dict) -> Dict[str, float]:
         """main.py:684-707."""
-        if self._cu_budget:
-            ops.set_cu_budget(self._cu_budget)
+        # (a micro-step that only accumulates issues no collective: the planner keeps all CUs there)
+        budget = self._cu_budget if not (self.accumulate_steps > 1 and self._micro < self.accumulate_steps - 1) else 0
+        if budget:
+            ops.set_cu_budget(budget)
         try:
             ms = self.reducer.step_stream
             if ms is None:
@@ -735,10 +811,12 @@ class Trainer:
             cur.wait_stream(ms)
             return out
         finally:
-            if self._cu_budget:
+            if budget:
                 ops.set_cu_budget(0)  # generation / evaluation have no collective beside them
 
     def _train_step(self, batch: Dict) -> Dict[str, float]:
+        if self.accumulate_steps > 1:
+            return self._micro_step(batch)
         m, st, eng = self.model, self.model.store, self.model.engine
         px, labels, mask, dec_in, pos, B, T = self._prep(batch)
         seed = (self.dropout_seed + self.step * 0x9E3779B1) & 0xFFFFFFFF  # split(dropout_rng) per step (main.py:686)
@@ -769,7 +847,7 @@ class Trainer:
                             after=self._adamw_shared_late if (self._split_shared and not self._late_done) else None)
         if not self.overlap_optimizer:
             ops.adamw(st.master, st.m, st.v, st.grad, None if st.lp is st.master else st.lp, self.hyper, self.b1, self.b2, self.eps,
-                      self.wd, grad_scale=1.0 / self.world)
+                      self.wd, grad_scale=self._gscale)
             eng.fp8_requantize_range(0, st.numel)
         m.invalidate_params_cache(by_optimizer=True)
         if m.device.type == "cuda":
@@ -784,6 +862,73 @@ class Trainer:
             return {"loss": out[0], "learning_rate": out[1]}
         self.metrics_buf[0:1].copy_(loss)
         self.metrics_buf[1:2].copy_(self.hyper[0:1])  # lr, device to device (a Python scalar assigned into a device tensor syncs)
+        return self._pmean_metrics()
+
+    def _micro_step(self, batch: Dict) -> Dict[str, float]:
+        """`train_step` under accumulate_steps = N > 1: micro-step j = self._micro of the pending optimizer step.  j < N - 1: backward
+        into `grad`, then `acc (+)= grad` — per bucket on the optimizer stream as backward reports it, no exchange, no optimizer, the
+        weights untouched.  j = N - 1: the step of `_train_step` on grad + acc with grad_scale 1 / (world * N)."""
+        m, st, eng = self.model, self.model.store, self.model.engine
+        N, j = self.accumulate_steps, self._micro
+        final = j == N - 1
+        px, labels, mask, dec_in, pos, B, T = self._prep(batch)
+        seed = virtual_rank_dropout_seed(self.seed, self.rank, self.step, N, j)
+        if j == 0:  # (lr, count) of the pending optimizer step: AdamW reads them on the last micro-step, the metrics on every one
+            self._set_hyper(float(self.lr_fn(self.step)), float(self.step + 1))
+        r = self.reducer
+        per_bucket = r.on_ready is not None
+        if final:
+            # one rank: every AdamW launch reads g + acc.  Several: the sum joins the gradient in front of each all-reduce, AdamW is the plain one
+            self._use_acc = self.world == 1
+            r.start_step(pre_exchange=self._pre_cb if self.world > 1 else None)
+        else:
+            r.start_step(local=True, on_ready=self._acc_cb if per_bucket else None, ready_when=self._when_acc)
+        eng.grad_progress = r.progress if r.active else None
+        # the sparse input-embedding rows: scattered locally while accumulating (acc carries them), exchanged on the last micro-step
+        eng.defer_embed = final and self.world > 1
+        self._late_done = False
+        eng.on_embed_rows = self._embed_rows_done if (final and self.world == 1 and self._split_shared and per_bucket
+                                                      and self._late_early) else None
+        try:
+            with ops.pinned_stream():
+                if final and self._split_shared:  # the rows of THIS micro-step's ids only: acc is already complete for every row
+                    self._flag_embedding_rows(self._pack[1] if self._pack is not None else dec_in.reshape(-1))
+                if self._pack is not None:
+                    pack, ids_p, pos_p = self._pack
+                    loss = eng.loss_and_grads(px, ids_p, pos_p, None, labels.reshape(-1), B, T, label_smoothing=self.ls, seed=seed,
+                                              rows=self._rows, row_labels=self._row_labels, pack=pack)
+                else:
+                    loss = eng.loss_and_grads(px, dec_in.reshape(-1), pos.reshape(-1), mask, labels.reshape(-1), B, T,
+                                              label_smoothing=self.ls, seed=seed, rows=self._rows, row_labels=self._row_labels)
+            eng.on_embed_rows = None
+            if not final:
+                r.finish()
+                if not per_bucket:  # overlap_optimizer=False: one pass over the whole buffer behind backward, like its AdamW
+                    ops.grad_accumulate(st.acc, st.grad, init=j == 0)
+                self._loss_sum = loss.reshape(1).clone() if j == 0 else self._loss_sum + loss.reshape(1)
+                self._micro = j + 1
+                out = torch.cat((loss.reshape(1), self.hyper[0:1]))
+                return {"loss": out[0], "learning_rate": out[1]}
+            r.finish(before=self._scatter_embedding_rows if self.world > 1 else None,
+                     after=self._adamw_shared_late if (self._split_shared and not self._late_done) else None)
+            if not self.overlap_optimizer:
+                ops.adamw(st.master, st.m, st.v, st.grad, None if st.lp is st.master else st.lp, self.hyper, self.b1, self.b2, self.eps,
+                          self.wd, grad_scale=self._gscale, acc=st.acc if self._use_acc else None)
+        finally:
+            eng.on_embed_rows = None
+            self._use_acc = False
+        m.invalidate_params_cache(by_optimizer=True)
+        if m.device.type == "cuda":
+            eng.refresh_shared_T(ops.role_stream(m.device, "aux"), st.version)
+        self.step += 1
+        self._micro = 0
+        mean = (self._loss_sum + loss.reshape(1)) * (1.0 / N)  # the reference's pmean'd loss over the N virtual ranks; stays on the device
+        self._loss_sum = None
+        if self.world == 1:
+            out = torch.cat((mean, self.hyper[0:1]))
+            return {"loss": out[0], "learning_rate": out[1]}
+        self.metrics_buf[0:1].copy_(mean)
+        self.metrics_buf[1:2].copy_(self.hyper[0:1])
         return self._pmean_metrics()
 
     def eval_step(self, batch: Dict) -> Dict[str, float]:
@@ -811,6 +956,9 @@ class Trainer:
 
         from .checkpoint import save_train_state
 
+        if self._micro != 0:
+            raise RuntimeError(f"save_checkpoint in the middle of a gradient accumulation ({self._micro} of {self.accumulate_steps} micro-steps "
+                               "taken): the running gradient sum is not part of a checkpoint; save after the optimizer step")
         ckpt = os.path.join(save_dir, f"ckpt-{self.step - 1}")
         if self.rank != 0 or (os.path.exists(ckpt) and not overwrite):  # main.py:304-305
             return ckpt
@@ -826,6 +974,7 @@ class Trainer:
         from .checkpoint import load_train_state
 
         self.step = load_train_state(ckpt_dir, self.model.store)
+        self._micro = 0  # a pending accumulation belongs to the state that was replaced
         self.model.invalidate_params_cache()
         return self.step
 
