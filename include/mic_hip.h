@@ -317,7 +317,9 @@ int mic_kv_append(int dtype, int R, int HD, int max_len, int cur, const void* k,
 /* ---------------------------------------------------------------------------------------------
  * ViT embeddings (3P FlaxCLIPVisionEmbeddings)
  *   im2col: pixels NHWC fp32 [B][img][img][3] -> patches [B*g*g][ps*ps*3] (dtype), k order (u,v,c) = HWIO.
- *           trunc_int32 = 1 reproduces encode()'s cast of pixel_values to int32 (modeling:330).
+ *           trunc_int32 = 1 reproduces encode()'s cast of pixel_values to int32 (modeling:330) as VALUES: it rounds toward zero
+ *           with truncf, so a pixel in (-1, 0) is stored as -0.0 where the cast through int32 gives +0.0 (the two compare equal).
+ *           img % ps == 0.  Vector path: (ps * 3) % 8 == 0, ldp % 8 == 0, pixels and patches 16-B aligned; element path otherwise.
  *   assemble: x[b,0] = cls + pos[0]; x[b,1+p] = patch_out[b,p] + pos[1+p]
  *   assemble_bwd: dpatch = dx[:,1:], dpos += sum_b dx, dcls += sum_b dx[:,0]   (fp32 atomics; caller zeroes)
  * ------------------------------------------------------------------------------------------- */
@@ -341,8 +343,16 @@ int mic_embed_bwd(int dtype, int rows, int width, const int32_t* ids, const int3
 /* The token-embedding scatter of the DATA-PARALLEL step (main.py:698 pmean of a gradient whose embedding part is sparse): dtable[ids[i]]
  * += scale * dh[i] for the n all-gathered rows of all ranks, DETERMINISTIC — the occurrences of an id are added by a single writer in a
  * fixed order (a function of the index set only), so every rank computes the same bits and the replicas stay identical (fp32 atomics do
- * not guarantee that).  ids < 0 are skipped (padding); n <= 65536, width % 64 == 0.  ws: mic_embed_rows_add_det_ws(vocab) ints, initialised ONCE by the caller (ints [0, vocab) 0x7fffffff,
- * [vocab, 2 vocab) 0, [2 vocab, 3 vocab) -1, the rest 0); the call leaves its first 3 vocab + 1 ints in that state (the rest is scratch). */
+ * not guarantee that).  ids < 0 are skipped (padding); every other id must be < vocab (it indexes the workspace: a larger one writes
+ * past owner[] into count[]); n <= 65536, width % 64 == 0, ids and dh 16-B aligned.  ws: mic_embed_rows_add_det_ws(vocab) ints,
+ * initialised ONCE by the caller (ints [0, vocab) 0x7fffffff, [vocab, 2 vocab) 0, [2 vocab, 3 vocab) -1, the rest 0); the call leaves its
+ * first 3 vocab + 1 ints in that state (the rest is scratch).  Table rows no id names are not written.
+ * The order, in fp32 (i: the positions of one id in ids[], ascending):
+ *   one or two occurrences:  dtable[id] += (dh[first] (+ dh[last])) * scale;
+ *   more:  sixteen partial rows, each summed from 0 in ascending i — position i belongs to bitmap word w = i >> 5 and goes to partial
+ *          (w ^ (w >> 4)) % 16 — then t = 0 + partial[0] + ... + partial[15], dtable[id] += t * scale.
+ * The product with scale and the add to the table may be contracted into one fused operation (identical bits for a power-of-two scale).
+ * A call refused with MIC_EINVAL (dtype included) has launched nothing: dtable and the workspace are as found. */
 int mic_embed_rows_add_det(int dtype, int n, int width, int vocab, const int32_t* ids, const void* dh, float scale, float* dtable,
                            int32_t* ws, void* stream);
 int64_t mic_embed_rows_add_det_ws(int vocab);
@@ -386,8 +396,9 @@ int mic_ce_bwd_q8(int rows, int V, int Vpad, const void* logits, int ld, const i
                   float label_smoothing, const float* row_lse, const float* denom, float loss_scale, const mic_fp8_out* q8,
                   float* colsum, float* label_coef, void* stream);
 /* The label entries of dlogits (mic_ce_bwd_q8 label_coef; bf16 E [V][lde] and h [rows][ldh]): dx_slab[m][0 .. width) = coef[m] *
- * E[labels[m]][:] — one more fp32 slab for mic_sum_slabs behind the split-K dX GEMM — and dE[labels[m]][:] += coef[m] * h[m][:] (fp32
- * atomics into the gradient the dE GEMM has written). */
+ * E[labels[m]][:] (one fp32 product) — one more fp32 slab for mic_sum_slabs behind the split-K dX GEMM — and dE[labels[m]][:] += coef[m]
+ * * h[m][:] (fp32 atomics into the gradient the dE GEMM has written).  A row with coef[m] == 0 writes +0 bits to dx_slab[m][:], reads
+ * neither E nor h and leaves dE untouched.  width, lde, ldh multiples of 8, ldx of 4. */
 int mic_head_label_terms(int rows, int width, const int32_t* labels, const float* coef, const void* E, int lde, const void* h, int ldh,
                          float* dx_slab, int ldx, float* dE, int ldde, void* stream);
 /* mic_ce_bwd (bf16 logits) that ALSO writes the transposed gradient dlogits_t [Vpad][ld_t] (bf16; columns rows .. rows_pad — a
@@ -406,13 +417,15 @@ int mic_transpose_bf16(int rows, int rows_pad, int cols, const void* src, int ld
 /* ---------------------------------------------------------------------------------------------
  * Small reductions / elementwise
  * ------------------------------------------------------------------------------------------- */
-/* out[n] (+)= sum_m x[m,n]  (bias gradients).  accumulate=0 overwrites. */
+/* out[n] (+)= sum_m x[m,n]  (bias gradients; fp32 atomics between the row slices).  accumulate=0 overwrites.  16-B row vectors:
+ * ld % 8 == 0 and x 16-B aligned (bf16 and fp32 alike); columns cols .. ld are not read.  A call refused with MIC_EINVAL — these
+ * conditions and the dtype, for mic_colsum_grouped / mic_colsum_q8_grouped on ANY item — has neither zero-filled nor added to an output. */
 int mic_colsum(int dtype, int rows, int cols, const void* x, int ld, float* out, int accumulate, void* stream);
 /* several column sums (always accumulating into caller-zeroed outputs) in one launch per 8 items */
 typedef struct { const void* x; float* out; int rows, cols, ld; } mic_colsum_item;
 int mic_colsum_grouped(int dtype, const mic_colsum_item* items, int count, void* stream);
 /* the same over fp8 tensors (fused emission): out[c] += scale_inv[0] * sum_r fp8(x[r][c]) — the bias gradient of an fp8 projection from
- * the bytes its dy exists as; cols, ld multiples of 8 */
+ * the bytes its dy exists as (OCP e4m3fn / e5m2, subnormals included); cols, ld multiples of 8, x 8-B aligned, fmt MIC_E4M3 or MIC_E5M2 */
 typedef struct { const void* x; float* out; const float* scale_inv; int rows, cols, ld, fmt; } mic_colsum_q8_item;
 int mic_colsum_q8_grouped(const mic_colsum_q8_item* items, int count, void* stream);
 /* keep-mask (uint8, 1 = keep) that the fused dropout epilogues use for (seed, p) over n elements */
@@ -437,7 +450,8 @@ int mic_comm_emulate(const void* src, void* dst, int64_t bytes, float micros, in
  * the cross-entropy only on the label positions whose loss mask is 1 (main.py:678: masked positions contribute exactly 0). */
 int mic_copy_rows(int dtype, int n, int width, const void* src, int ld_src, const int32_t* src_idx, void* dst, int ld_dst,
                   const int32_t* dst_idx, void* stream);
-/* dst[r][c] (dst_dtype, ld_dst) = src[r][c] (src_dtype, ld_src) */
+/* dst[r][c] (dst_dtype, ld_dst) = src[r][c] (src_dtype, ld_src); fp32 -> bf16 rounds to nearest even (overflow to inf, fp32 subnormals
+ * kept), a NaN stays a NaN; the other three pairs are exact.  mic_cast: the same over n contiguous elements. */
 int mic_cast2d(int src_dtype, int dst_dtype, int rows, int cols, const void* src, int ld_src, void* dst, int ld_dst,
                void* stream);
 

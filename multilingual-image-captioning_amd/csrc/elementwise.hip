@@ -372,6 +372,8 @@ extern "C" int mic_embed_rows_add_det(int dtype, int n, int width, int vocab, co
                                       int32_t* ws, void* stream) {
   MIC_CHECK(n > 0 && n <= 65536 && width > 0 && width % 64 == 0 && vocab > 0 && ids && dh && dtable && ws && ((uintptr_t)dh & 15) == 0 && ((uintptr_t)ids & 15) == 0,
             "mic_embed_rows_add_det: bad args (n <= 65536, width %% 64 == 0, 16-B aligned rows, workspace of mic_embed_rows_add_det_ws(vocab) ints)");
+  // every refusal comes before the first launch: a call that returns MIC_EINVAL has touched neither dtable nor the workspace
+  MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_embed_rows_add_det: bad dtype %d", dtype);
   int* owner = ws; int* count = ws + vocab; int* last = ws + 2 * (size_t)vocab; int* mcount = ws + 3 * (size_t)vocab; int* mlist = mcount + 1;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(det_owner_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, ids, owner, count, last);
@@ -872,14 +874,23 @@ __global__ __launch_bounds__(256) void colsum_kernel(ColsumTable tab) {
     atomicAdd(I.out + c, s);
   }
 }
+// every requirement of mic_colsum / mic_colsum_grouped, checked over ALL items before the first memset or launch: a refused call
+// leaves its outputs as found
+static int colsum_validate(int dtype, const mic_colsum_item* items, int count) {
+  MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_colsum: bad dtype %d", dtype);
+  for (int i = 0; i < count; ++i) {
+    const mic_colsum_item& a = items[i];
+    MIC_CHECK(a.rows > 0 && a.cols > 0 && a.x && a.out, "mic_colsum: bad args");
+    MIC_CHECK(a.ld % 8 == 0 && ((uintptr_t)a.x & 15) == 0, "mic_colsum: rows must be 16-B aligned (ld %% 8 == 0, x 16-B aligned)");
+  }
+  return MIC_OK;
+}
 static int colsum_launch(int dtype, const mic_colsum_item* items, int count, void* stream) {
   ColsumTable tab;
   tab.count = count;
   int blocks = 0;
   for (int i = 0; i < count; ++i) {
     const mic_colsum_item& a = items[i];
-    MIC_CHECK(a.rows > 0 && a.cols > 0 && a.x && a.out, "mic_colsum: bad args");
-    MIC_CHECK(a.ld % 8 == 0 && ((uintptr_t)a.x & 15) == 0, "mic_colsum: rows must be 16-B aligned");
     ColsumItem& t = tab.it[i];
     t.x = a.x; t.out = a.out; t.rows = a.rows; t.cols = a.cols; t.ld = a.ld;
     t.gx = (a.cols + 255) / 256;
@@ -940,14 +951,17 @@ __global__ __launch_bounds__(256) void colsum_q8_kernel(Colsum8Table tab) {
 }
 extern "C" int mic_colsum_q8_grouped(const mic_colsum_q8_item* items, int count, void* stream) {
   MIC_CHECK(items && count >= 1, "mic_colsum_q8_grouped: bad args");
+  for (int i = 0; i < count; ++i) {  // all items before the first launch: a refused call has added nothing
+    const mic_colsum_q8_item& a = items[i];
+    MIC_CHECK(a.rows > 0 && a.cols > 0 && a.x && a.out && a.scale_inv, "mic_colsum_q8_grouped: bad item %d", i);
+    MIC_CHECK(a.cols % 8 == 0 && a.ld % 8 == 0 && ((uintptr_t)a.x & 7) == 0 && (a.fmt == MIC_E4M3 || a.fmt == MIC_E5M2), "mic_colsum_q8_grouped: cols, ld multiples of 8; fmt");
+  }
   for (int i0 = 0; i0 < count; i0 += COLSUM_MAX) {
     Colsum8Table tab;
     tab.count = count - i0 < COLSUM_MAX ? count - i0 : COLSUM_MAX;
     int blocks = 0;
     for (int i = 0; i < tab.count; ++i) {
       const mic_colsum_q8_item& a = items[i0 + i];
-      MIC_CHECK(a.rows > 0 && a.cols > 0 && a.x && a.out && a.scale_inv, "mic_colsum_q8_grouped: bad item %d", i0 + i);
-      MIC_CHECK(a.cols % 8 == 0 && a.ld % 8 == 0 && ((uintptr_t)a.x & 7) == 0 && (a.fmt == MIC_E4M3 || a.fmt == MIC_E5M2), "mic_colsum_q8_grouped: cols, ld multiples of 8; fmt");
       Colsum8Item& t = tab.it[i];
       t.x = (const uint8_t*)a.x; t.out = a.out; t.scale_inv = a.scale_inv; t.rows = a.rows; t.cols = a.cols; t.ld = a.ld; t.fmt = a.fmt;
       t.gx = (a.cols + 255) / 256;
@@ -964,13 +978,14 @@ extern "C" int mic_colsum_q8_grouped(const mic_colsum_q8_item* items, int count,
   return MIC_OK;
 }
 extern "C" int mic_colsum(int dtype, int rows, int cols, const void* x, int ld, float* out, int accumulate, void* stream) {
-  MIC_CHECK(rows > 0 && cols > 0 && x && out, "mic_colsum: bad args");
-  if (!accumulate) hipMemsetAsync(out, 0, sizeof(float) * cols, (hipStream_t)stream);
   mic_colsum_item it = {x, out, rows, cols, ld};
+  if (int rc = colsum_validate(dtype, &it, 1)) return rc;
+  if (!accumulate) hipMemsetAsync(out, 0, sizeof(float) * cols, (hipStream_t)stream);
   return colsum_launch(dtype, &it, 1, stream);
 }
 extern "C" int mic_colsum_grouped(int dtype, const mic_colsum_item* items, int count, void* stream) {
   MIC_CHECK(items && count >= 1, "mic_colsum_grouped: bad args");
+  if (int rc = colsum_validate(dtype, items, count)) return rc;
   for (int i = 0; i < count; i += COLSUM_MAX) {
     const int n = count - i < COLSUM_MAX ? count - i : COLSUM_MAX;
     if (int rc = colsum_launch(dtype, items + i, n, stream)) return rc;
