@@ -8,13 +8,16 @@ pad rows stay zero) so weight-gradient GEMMs can reduce over the padded row coun
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import os
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib as L
 from . import ops
+from .fp8_state import E4M3, E5M2, Q8, Fp8State, Fp8Views
 from .params import ParamStore, _rup
 
 ROWPAD = 128
@@ -28,7 +31,7 @@ def _mix(seed: int, site: int) -> int:
     return x & 0xFFFFFFFF
 
 
-class Engine:
+class Engine(Fp8Views):
     def __init__(self, store: ParamStore):
         self.P = store
         self.dt = store.dtype
@@ -44,9 +47,11 @@ class Engine:
         self.embed_rows = None     # (ids, dh0 buffer, M) of the last backward when deferred
         self._dw_queue = []
         self._cs_queue = []
+        self._dw8_queue = []     # (fp8 projections: their weight-gradient GEMMs ...
+        self._cs8_queue = []     # ... and bias gradients: column sums over the e5m2 bytes of dy)
         self.on_free = []  # callables run by free_buffers() before the buffers go (decode plans drop their captured graphs)
         self.fp8 = False
-        import os
+        self.f8: Optional[Fp8State] = None  # the fp8 operands' state while the projections run as fp8 GEMMs (set_gemm_dtype)
         self.use_head_stats = os.environ.get("MIC_HEAD_STATS", "1") != "0"  # softmax partials out of the LM-head GEMM (A/B switch)
         self.grad_progress = None  # callable(offset): every gradient with flat offset < offset is final (DDP overlap)
         self.on_embed_rows = None  # callable(): single process, right behind the input-embedding scatter at the end of decoder backward
@@ -62,16 +67,13 @@ class Engine:
         self._dw_stream = None
         # LM-head backward as NT launches of the four-wave kernel (k-contiguous copies: dlogits^T from the CE backward, h^T, E^T);
         # MIC_HEAD_NT=0: the k-major launches of rounds 1-4 (A/B)
-        import os as _os
-        self.head_nt = _os.environ.get("MIC_HEAD_NT", "1") != "0"
+        self.head_nt = os.environ.get("MIC_HEAD_NT", "1") != "0"
         # LayerNorm backward: gamma / beta gradients as per-block partial sums reduced later with the layer's weight-gradient launches
         # (no atomics on the critical path, a fixed summation order); MIC_LN_PARTIALS=0: fp32 atomics inside the kernel (A/B)
-        self.ln_partials = _os.environ.get("MIC_LN_PARTIALS", "1") != "0"
+        self.ln_partials = os.environ.get("MIC_LN_PARTIALS", "1") != "0"
         self._lnp_queue = []
         self._head_nt_state = None   # (dlogits^T, Kp) of the CE backward that has just run
         self.fp8_head = 0            # fp8 GEMM mode: the tied head's GEMMs on fp8 operands too (set_gemm_dtype)
-        self._head8_state = None
-        self._head_x8 = None
         self._ET_version, self._ET_event = -1, None
         self._dw_events = []
         # weight-gradient launches behind every n-th layer: 2 in fp8 mode (its two GEMM streams alternate rather than overlap — half as
@@ -82,8 +84,6 @@ class Engine:
         self._ckv_block_name = None  # set while the all-layer cross k/v weight gradient (one launch) sits in the dW queue
 
     # ------------------------------------------------------------------ fp8 GEMM operands (BASELINE configs[4])
-    FP8_KINDS = ("qkv", "cq", "ckv", "fc1", "fc2")  # the QKV and FFN projections of both towers; out-projections and the head stay bf16
-
     def set_gemm_dtype(self, name, scaling: str = "delayed", head: Optional[str] = None):
         """"fp8": the QKV / FFN projections run as OCP fp8 GEMMs — e4m3 activations and weights, e5m2 gradients, one scale per
         tensor, fp32 accumulate (forward, dX and dW).  None / "bf16": the storage dtype.
@@ -96,12 +96,12 @@ class Engine:
         by ~lr, so the one-step-old maximum is the current one to fp8 precision and the amax pass over 246 M parameters goes;
         weights that arrive any other way (params setter, checkpoint restore) start again from their current amax.
         Under delayed scaling a tensor WITH a scale history is not quantised by a launch of its own: its producer (LayerNorm forward /
-        backward, the GELU / dGELU epilogue of the fp8 GEMM, attention backward) writes the fp8 bytes (`_q8_target`, `fp8_fused`);
-        the weight copies of the next pass are made on a side stream behind the optimizer (`fp8_refresh_weights`).
+        backward, the GELU / dGELU epilogue of the fp8 GEMM, attention backward) writes the fp8 bytes (`Fp8State.target`, `fp8_fused`);
+        the weight copies of the next pass are made on a side stream behind the optimizer (`Fp8State.refresh_weights`).
         head = "all" | "bwd" | "0" (default: MIC_FP8_HEAD, else "all"): the tied LM head's three GEMMs / its two backward GEMMs / none
-        of them on fp8 operands (see below)."""
+        of them on fp8 operands (see fp8_state.py).  The operands' state lives in `self.f8` (None outside the fp8 mode)."""
         if name in (None, "bf16", "bfloat16", "f32", "float32"):
-            self.fp8 = False
+            self.fp8, self.f8 = False, None
             return
         if name != "fp8":
             raise ValueError(f"unknown gemm_dtype {name!r}")
@@ -109,81 +109,13 @@ class Engine:
             raise ValueError(f"fp8 scaling must be 'delayed' or 'current', got {scaling!r}")
         if self.dt != torch.bfloat16:
             raise ValueError("gemm_dtype='fp8' needs the bfloat16 storage mode (dtype=bfloat16)")
-        import os as _os
-        P = self.P
-        self.fp8 = True
-        self.fp8_scaling = scaling
-        # the cross-attention k/v projections of all layers as ONE fp8 matrix "ckvcat" (one scale) when they run hoisted (ckv_hoisted)
-        kinds = tuple(k for k in self.FP8_KINDS if not (k == "ckv" and self._ckv_hoist))
-        names = [f"dec{l}.{k}" for l in range(P.L) for k in kinds] + [f"vit{l}.{k}" for l in range(P.vL) for k in ("qkv", "fc1", "fc2")]
-        if self._ckv_hoist:
-            names.append("ckvcat")
-        # the tied LM head in fp8 too (MIC_FP8_HEAD = all | bwd | 0; default all): its three GEMMs are 3.7 of the step's 8.4 TFLOP.
-        # Backward: dE and dX read ONE e5m2 copy of dlogits written by the CE backward under a closed-form scale (`mic_ce_bwd_q8`; no
-        # in-place gradient, no transposed copy), the e4m3 copies of E / E^T (re-made with the other weights) and the e4m3 final hidden
-        # states; forward ("all"): the logits from the e4m3 operands, softmax partials as in bf16.  "bwd": forward stays bf16; "0": the
-        # head as in the bf16 mode.  Needs the reduction dimensions (d, Vpad) in whole 128-byte fragments.
-        mode = head if head is not None else _os.environ.get("MIC_FP8_HEAD", "all")
-        if mode not in ("0", "bwd", "all"):
-            raise ValueError(f"MIC_FP8_HEAD / head={mode!r}: 0 | bwd | all")
-        self.fp8_head = {"0": 0, "bwd": 1, "all": 2}[mode] if (P.d % 128 == 0 and P.Vpad % 128 == 0) else 0
-        if self.fp8_head:
-            names.append("shared")
-        self._head8_state = None  # (dlogits as e5m2 [rows][Vpad], its scale state) of the CE backward that has just run
-        self._head_x8 = None      # (final hidden states as e4m3, state) of this pass
-        self._w8 = {}
-        self._w8_state = torch.zeros((len(names), 2), dtype=torch.float32, device=self.dev)
-        for i, n in enumerate(names):
-            N, K = self._w8_src(n).shape
-            self._w8[n] = (torch.empty((N, K), dtype=torch.float8_e4m3fn, device=self.dev),   # [out][in]: forward  x W^T
-                           torch.empty((K, N), dtype=torch.float8_e4m3fn, device=self.dev),   # [in][out]: dX = dy W
-                           self._w8_state[i])
-        self._w8_stale = True
-        self._w8_part = torch.zeros((len(names), ops.fp8_amax_partials()), dtype=torch.float32, device=self.dev) if scaling == "delayed" else None
-        self._w8_seen = False  # delayed scaling: _w8_state carries the amax recorded by the previous quantiser pass
-        # delayed scaling: the optimizer re-quantises a weight right behind its AdamW pass (`fp8_requantize_range`, on the optimizer's
-        # stream, under backward) — names done since the last pass; when that is all of them the next pass only rolls the amax
-        self._w8_fresh = set()
-        # (opt-in, MIC_FP8_REQUANT_OPT=1: measured 0.03 - 0.2 ms per step, inside the noise, for ~8 more launches per step — the default
-        # re-quantises all weights in 11 launches at the start of the next pass)
-        self._w8_requant_opt = _os.environ.get("MIC_FP8_REQUANT_OPT", "0") == "1"
-        self._w8_async = _os.environ.get("MIC_FP8_W8_ASYNC", "1") != "0"  # (A/B: 0 = weights re-quantised at the start of the next pass, on its stream)
-        self._w8_event = None
-        self._w8_rolled = False  # this step's roll of the weights' amax has been issued (first of the two refresh calls)
-        self._w8_index = {n: i for i, n in enumerate(names)}
-        segs = P.segs
-        def span(n):
-            if n == "ckvcat":
-                return segs["dec0.ckv.w"].offset, segs[f"dec{P.L - 1}.ckv.w"].offset + segs[f"dec{P.L - 1}.ckv.w"].numel
-            sg = segs["shared" if n == "shared" else n + ".w"]
-            return sg.offset, sg.offset + sg.numel
-        self._w8_span = {n: span(n) for n in names}
-        # one (amax, 1/scale) slot per quantised activation / gradient tensor; delayed scaling: + its table of partial maxima
-        self._a8_state = torch.zeros((1024, 2), dtype=torch.float32, device=self.dev)
-        self._a8_part = torch.zeros((1024, ops.fp8_amax_partials()), dtype=torch.float32, device=self.dev) if scaling == "delayed" else None
-        self._a8_slots: Dict[str, int] = {}
-        self._a8_ready = set()   # delayed scaling: tags whose slot carries the previous pass's amax
-        self._a8_cache: Dict = {}
-        self._dw8_queue = []
-        self._cs8_queue = []     # bias gradients of the fp8 projections: column sums over the e5m2 bytes of dy
-        self._x8: Dict[str, tuple] = {}  # wname -> (q, state) of the Linear's input as quantised in the training forward (dW reads it)
-        # fused emission: under delayed scaling the PRODUCER of an operand (LayerNorm, GELU / dGELU epilogue, attention backward)
-        # writes the fp8 bytes itself once the tensor has a scale history (from its second pass on); MIC_FP8_FUSED=0: every operand
-        # through mic_fp8_quantize again (A/B)
-        self.fp8_fused = scaling == "delayed" and self.ln_partials and _os.environ.get("MIC_FP8_FUSED", "1") != "0"
-
-    def _w8_src(self, name: str):
-        """the bf16 matrix behind the fp8 weight entry `name`"""
-        if name == "shared":
-            return self.P.w("shared")
-        return self.P.ckv_cat("w")[0] if name == "ckvcat" else self.P.w(name + ".w")
+        self.f8 = Fp8State(self.P, self.buf, ROWPAD, scaling, head, self._ckv_hoist, self.ln_partials)
+        self.fp8, self.fp8_scaling, self.fp8_head = True, scaling, self.f8.head
 
     def storage_dtype_gemms(self):
         """context: every Linear runs in the storage dtype (bf16) even when the trainer switched the projections to fp8 — the
         inference entry points (`encode`, `decode`, `generate`) are not part of a train / eval pass: nothing re-quantises the
         weights for them or rolls the activation scales, so fp8 launches there would read stale (or never written) copies"""
-        import contextlib
-
         @contextlib.contextmanager
         def ctx():
             keep = self.fp8
@@ -194,172 +126,26 @@ class Engine:
                 self.fp8 = keep
         return ctx()
 
-    def fp8_weights_changed(self, by_optimizer: bool = False):
-        self._w8_stale = True
-        if not by_optimizer:
-            self._w8_seen = False
-            self._w8_fresh = set()
-
-    def _w8_items_all(self):
-        """the 84 weight items of a delayed-scaling quantiser pass, built once (raw pointers into persistent buffers: the flat bf16
-        parameter copy, the fp8 copies, the scale slots) — building them was 0.2 ms of host time in the gap between two steps"""
-        key = (self.P.lp.data_ptr(), id(self._w8))
-        if getattr(self, "_w8_items_key", None) != key:
-            self._w8_items = [ops.fp8_item(self._w8_src(n), q.shape[0], q.shape[1], st, torch.float8_e4m3fn, q=q, qT=qT,
-                                           amax_next=self._w8_part[i]) for i, (n, (q, qT, st)) in enumerate(self._w8.items())]
-            self._w8_items_key = key
-        return self._w8_items
-
-    def fp8_refresh_weights(self, side, upto: Optional[int] = None, wait_event=None):
-        """Trainer (delayed scaling): roll the weights' amax and re-quantise them for the NEXT pass on `side` instead of in front of that
-        pass.  Two calls per step: `upto` = flat offset up to which the optimizer passes have been issued (`wait_event`: recorded on
-        the optimizer's stream behind them) — at the end of decoder backward: the decoder's weights go now, under the ViT's backward;
-        then the final call (upto None), behind everything the current stream has enqueued, takes the rest beside the host-issued glue
-        between two steps.  The first fp8 GEMM of the next pass waits for the final call's event (`_w8_wait`)."""
-        if not (self.fp8 and self.fp8_scaling == "delayed" and self._w8_seen and self._w8_async):
-            return
-        items = self._w8_items_all()
-        names = list(self._w8)
-        if upto is not None:
-            todo = [i for i, n in enumerate(names) if self._w8_span[n][1] <= upto and n not in self._w8_fresh]
-            if not todo:
-                return
-            with torch.cuda.stream(side):
-                if wait_event is not None:
-                    side.wait_event(wait_event)
-                with ops.pinned_stream():
-                    if not self._w8_rolled:
-                        ops.fp8_roll_amax(self._w8_state, self._w8_part, len(names))
-                        self._w8_rolled = True
-                    ops.fp8_quantize([items[i] for i in todo], amax_pass=False)
-            self._w8_fresh.update(names[i] for i in todo)
-            return
-        if not self._w8_stale:
-            return
-        todo = [i for i, n in enumerate(names) if n not in self._w8_fresh]
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            side.wait_event(ev)
-            with ops.pinned_stream():
-                if not self._w8_rolled:
-                    ops.fp8_roll_amax(self._w8_state, self._w8_part, len(names))
-                if todo:
-                    ops.fp8_quantize([items[i] for i in todo], amax_pass=False)
-            done = torch.cuda.Event()
-            done.record(side)
-        self._w8_event, self._w8_stale, self._w8_fresh, self._w8_rolled = done, False, set(), False
-
-    def _w8_wait(self):
-        if self._w8_event is not None:
-            torch.cuda.current_stream().wait_event(self._w8_event)
-            self._w8_event = None
-
-    def fp8_requantize_range(self, b: int, e: int):
-        """Optimizer side (delayed scaling): the weights whose flat segment ENDS in (b, e] have just been updated — the buckets arrive
-        in layout order on one stream, so everything before `e` is final — re-quantise them now, on the caller's stream (beside
-        backward), under the amax the step's begin rolled in; the next pass then finds its fp8 weight copies ready."""
-        if not (self.fp8 and self.fp8_scaling == "delayed" and self._w8_seen and self._w8_requant_opt):
-            return
-        # (the tied embedding's flagged rows get their optimizer pass at the end of backward: its copies are left to fp8_refresh_weights)
-        todo = [n for n, (o, oe) in self._w8_span.items() if b < oe <= e and n not in self._w8_fresh and n != "shared"]
-        if not todo:
-            return
-        items = []
-        for n in todo:
-            q, qT, st = self._w8[n]
-            items.append(ops.fp8_item(self._w8_src(n), q.shape[0], q.shape[1], st, torch.float8_e4m3fn, q=q, qT=qT,
-                                      amax_next=self._w8_part[self._w8_index[n]]))
-        ops.fp8_quantize(items, amax_pass=False)
-        self._w8_fresh.update(todo)
-
     def _fp8_begin_pass(self):
-        """start of a forward(+backward) pass: re-quantise the weights if the optimizer moved them; current scaling: clear the
-        activation slots; delayed scaling: last pass's recorded amax becomes this pass's scale source"""
-        if not self.fp8:
-            return
-        if self._w8_stale and self.fp8_scaling == "delayed" and self._w8_seen and len(self._w8_fresh) == len(self._w8):
-            # every weight was re-quantised behind its optimizer pass: only the amax recorded there becomes current
-            ops.fp8_roll_amax(self._w8_state, self._w8_part, len(self._w8))
-            self._w8_stale = False
-        self._w8_fresh = set()
-        if self._w8_stale:
-            P = self.P
-            delayed = self.fp8_scaling == "delayed"
-            if delayed and self._w8_seen:
-                ops.fp8_roll_amax(self._w8_state, self._w8_part, len(self._w8))
-            else:
-                ops.zero(self._w8_state)
-                if delayed:
-                    ops.zero(self._w8_part)
-            self._w8_wait()  # (a side-stream refresh of older weights may still be writing the copies)
-            items = self._w8_items_all() if delayed else [ops.fp8_item(self._w8_src(n), q.shape[0], q.shape[1], st, torch.float8_e4m3fn, q=q, qT=qT)
-                                                          for (n, (q, qT, st)) in self._w8.items()]
-            ops.fp8_quantize(items, amax_pass=not (delayed and self._w8_seen))
-            self._w8_seen = delayed
-            self._w8_stale = False
-        n = len(self._a8_slots)
-        if self.fp8_scaling == "delayed":
-            if n:
-                ops.fp8_roll_amax(self._a8_state, self._a8_part, n)
-            self._a8_ready = set(self._a8_slots)
-        else:
-            ops.zero(self._a8_state[: max(n, 1)])
-        self._a8_cache = {}
-        self._x8 = {}
-        self._head_x8 = None
+        if self.fp8:
+            self.f8.begin_pass()
 
     def _fp8_ok(self, wname: str) -> bool:
-        return self.fp8 and wname.split(".")[-1] in self.FP8_KINDS and wname in self._w8
+        return self.fp8 and self.f8.ok(wname)
 
-    def _a8_slot(self, tag: str) -> int:
-        i = self._a8_slots.get(tag)
-        if i is None:
-            i = self._a8_slots[tag] = len(self._a8_slots)
-            if i >= self._a8_state.shape[0]:
-                raise RuntimeError("fp8: out of activation scale slots")
-        return i
+    def dy8_target(self, wname: str, par: int, cap: int):
+        """`Fp8State.dy_target` when the Linear `wname` runs in fp8, else None"""
+        return self.f8.dy_target(wname, par, cap) if self._fp8_ok(wname) else None
 
-    def _quant(self, x, rows: int, cols: int, tag: str, buf_tag: str, fmt, cache: bool = False):
-        """(q [rows][cols] fp8, state) of bf16 x through mic_fp8_quantize (the unfused path: tensors without a scale history, operands
-        no kernel of ours produces in fp8).  No transposed copy: the weight-gradient GEMM reads its operands k-major.  cache=True: x
-        keeps its contents for the rest of the pass (the encoder states every layer's cross-attention projects): quantised once."""
-        key = (x.data_ptr(), rows, cols, fmt)
-        hit = self._a8_cache.get(key) if cache else None
-        if hit is not None:
-            return hit
-        # sized by the CAPACITY of x (its row count is the step-independent [B*T] / [B*S] capacity), not by this step's valid rows:
-        # with packed decoder rows `rows` changes from step to step and a buffer per distinct count would never be freed
-        cap = max(int(x.shape[0]), _rup(rows, ROWPAD))
-        q = self.buf(buf_tag + ".q8", cap, cols, fmt)
-        slot = self._a8_slot(tag)
-        st = self._a8_state[slot]
-        delayed = self.fp8_scaling == "delayed"
-        item = ops.fp8_item(x, rows, cols, st, fmt, q=q, amax_next=self._a8_part[slot] if delayed else None)
-        ops.fp8_quantize([item], amax_pass=not (delayed and tag in self._a8_ready))
-        if cache:
-            self._a8_cache[key] = (q, st)
-        return q, st
-
-    def _q8_target(self, tag: str, buf_tag: str, rows_cap: int, cols: int, fmt):
-        """(q, state, fp8_out descriptor, (state, partials)) when the tensor `tag` can be EMITTED by its producer: fp8 GEMMs on, delayed
-        scaling, a scale history for this tensor (second pass on); else None: the producer writes bf16 and `_quant` follows."""
-        if not (self.fp8 and self.fp8_fused and tag in self._a8_ready):
-            return None
-        slot = self._a8_slot(tag)
-        st, part = self._a8_state[slot], self._a8_part[slot]
-        q = self.buf(buf_tag + ".q8", rows_cap, cols, fmt)
-        return q, st, ops.fp8_out(q, st, part), (st, part)
-
-    def ln_x8(self, x, ln: str, eps: float, a_name: str, cap: int, mean, rstd, rows: int, wname: str, q_tag: str, **kw):
-        """LayerNorm `ln` of x whose output feeds Linear `wname`: (a bf16 or None, x8 = (q, state) or None).  Fused fp8 emission when
+    def ln_q8(self, x, ln: str, eps: float, a_name: str, cap: int, mean, rstd, rows: int, wname: str, q_tag: str, **kw):
+        """LayerNorm `ln` of x whose output feeds Linear `wname`: (a bf16 or None, x8 = Q8 or None).  Fused fp8 emission when
         that Linear runs in fp8 and its input has a scale history: the normalised rows leave as e4m3 bytes only."""
         P = self.P
         width = x.shape[-1]
-        t = self._q8_target(wname + ".x", q_tag + wname.split(".")[-1] + ".x", cap, width, torch.float8_e4m3fn) if self._fp8_ok(wname) else None
+        t = self.f8.target(wname + ".x", q_tag + wname.split(".")[-1] + ".x", cap, width, E4M3) if self._fp8_ok(wname) else None
         if t is not None:
-            ops.layernorm_fwd(x, P.f32(ln + ".g"), P.f32(ln + ".b"), eps, None, mean, rstd, rows=rows, q8=t[2], **kw)
-            return None, (t[0], t[1])
+            ops.layernorm_fwd(x, P.f32(ln + ".g"), P.f32(ln + ".b"), eps, None, mean, rstd, rows=rows, q8=t.out, **kw)
+            return None, t.q8
         a = self.buf(a_name, cap, width)
         ops.layernorm_fwd(x, P.f32(ln + ".g"), P.f32(ln + ".b"), eps, a, mean, rstd, rows=rows, **kw)
         return a, None
@@ -404,27 +190,27 @@ class Engine:
     def linear(self, x, wname, out, M, *, act=0, zout=None, residual=None, drop_seed=None, bias=True, save_tag=None, fp8=True,
                stable_input=False, x8=None, out8=None):
         """save_tag (fp8 mode, training forward): the fp8 copy of x is kept under that name for the weight-gradient GEMM of backward
-        (dW = dy^T x reads dy and x k-major, as they lie).  x8 = (q, state): x already exists as fp8 bytes (fused emission by its
-        producer; `x` may be None).  out8 = `_q8_target(...)`: the result leaves as fp8 bytes (the GELU output of FFN-in, whose only
-        reader is the fp8 FFN-out projection); returns (q, state) then."""
+        (dW = dy^T x reads dy and x k-major, as they lie).  x8 (a Q8): x already exists as fp8 bytes (fused emission by its
+        producer; `x` may be None).  out8 (a Q8Target): the result leaves as fp8 bytes (the GELU output of FFN-in, whose only
+        reader is the fp8 FFN-out projection); returns its Q8 then."""
         P = self.P
         w = P.w(wname + ".w")
         N, K = w.shape
         p = self.p_drop if drop_seed is not None else 0.0
         if fp8 and self._fp8_ok(wname):
-            self._w8_wait()
-            wq, _, ws = self._w8[wname]
+            f8 = self.f8
+            f8.wait()
+            w8 = f8.weights[wname]
             if x8 is None:
-                x8 = self._quant(x, M, K, wname + ".x", (save_tag or "f8.") + wname.split(".")[-1] + ".x", torch.float8_e4m3fn,
-                                 cache=stable_input)
+                x8 = f8.quant(x, M, K, wname + ".x", (save_tag or "f8.") + wname.split(".")[-1] + ".x", E4M3, cache=stable_input)
             if save_tag is not None:
-                self._x8[wname] = x8
+                f8.saved[wname] = x8
             kw = dict(bias=P.f32(wname + ".b") if bias else None, act=act, zout=zout, residual=residual, dropout_p=p, dropout_seed=drop_seed or 0,
-                      a_scale_inv=x8[1][1:], b_scale_inv=ws[1:])
+                      a_scale_inv=x8.scale_inv, b_scale_inv=w8.scale_inv)
             if out8 is not None:
-                ops.gemm(x8[0], wq, out8[0], M, N, K, c_q8=out8[3], **kw)
-                return out8[0], out8[1]
-            return ops.gemm(x8[0], wq, out, M, N, K, **kw)
+                ops.gemm(x8.q, w8.q, out8.q, M, N, K, c_q8=out8.c_q8, **kw)
+                return out8.q8
+            return ops.gemm(x8.q, w8.q, out, M, N, K, **kw)
         return ops.gemm(x, w, out, M, N, K, bias=P.f32(wname + ".b") if bias else None, act=act, zout=zout,
                         residual=residual, dropout_p=p, dropout_seed=drop_seed or 0)
 
@@ -433,8 +219,8 @@ class Engine:
         """dW = dy^T x (fp32, overwrite), db = colsum(dy), optionally dx = (dy W) [* act'(zin)].
         defer=True queues the weight-gradient GEMM (nothing but the optimizer depends on it): the caller keeps dy and x
         intact until flush_dw() launches the layer's queue as ONE grouped GEMM (36..256-tile problems fill the chip
-        only together).  fp8 projections: dy8 = (q, state) when dy's producer emitted the e5m2 bytes itself (`dy` may be None),
-        dx8 = `_q8_target(...)` when dx is to leave as fp8 bytes (the dGELU-scaled dX of FFN-out = the dy of FFN-in); par = layer
+        only together).  fp8 projections: dy8 (a Q8) when dy's producer emitted the e5m2 bytes itself (`dy` may be None),
+        dx8 (a Q8Target) when dx is to leave as fp8 bytes (the dGELU-scaled dX of FFN-out = the dy of FFN-in); par = layer
         parity of the buffer an unfused dy is quantised into (it is read by the deferred launches of its layer)."""
         P = self.P
         w = P.w(wname + ".w")
@@ -443,16 +229,16 @@ class Engine:
         if self._fp8_ok(wname) and x_tag is not None:
             # fp8: dy as e5m2 bytes [M][N] — row-major for dX = dy W (NT against W^T, quantised once per step), k-major for
             # dW = dy^T x (TN: both operands as their producers wrote them); x as saved by the forward pass
-            kind = wname.split(".")[0].rstrip("0123456789") + "." + wname.split(".")[-1]
+            f8 = self.f8
             if dy8 is None:
-                dy8 = self._quant(dy, M, N, wname + ".dy", f"f8.{kind}.dy.{par}", torch.float8_e5m2)
-            x8 = self._x8.get(wname)
+                dy8 = f8.quant(dy, M, N, wname + ".dy", f8.dy_buf(wname, par), E5M2)
+            x8 = f8.saved.get(wname)
             if x8 is None:
                 raise RuntimeError(f"fp8 backward of {wname}: the forward pass did not keep the fp8 copy of its input (save_tag missing)")
-            _, wqT, ws = self._w8[wname]
-            ga = ops.gemm_args(dy8[0], x8[0], P.g(wname + ".w"), N, K, Mp, a_kmajor=True, b_kmajor=True, k_valid=M,
-                               a_scale_inv=dy8[1][1:], b_scale_inv=x8[1][1:])
-            cs = (dy8[0], P.g(wname + ".b"), dy8[1][1:], M, N) if bias else None  # (into the pre-zeroed atomic region)
+            w8 = f8.weights[wname]
+            ga = ops.gemm_args(dy8.q, x8.q, P.g(wname + ".w"), N, K, Mp, a_kmajor=True, b_kmajor=True, k_valid=M,
+                               a_scale_inv=dy8.scale_inv, b_scale_inv=x8.scale_inv)
+            cs = (dy8.q, P.g(wname + ".b"), dy8.scale_inv, M, N) if bias else None  # (into the pre-zeroed atomic region)
             if defer:
                 self._dw8_queue.append((ga, wname, bias))
                 if cs is not None:
@@ -462,9 +248,9 @@ class Engine:
                 if cs is not None:
                     ops.colsum_q8_grouped([cs])
             if dx8 is not None:
-                ops.gemm(dy8[0], wqT, dx8[0], M, K, N, zin=zin, dact=dact, a_scale_inv=dy8[1][1:], b_scale_inv=ws[1:], c_q8=dx8[3])
+                ops.gemm(dy8.q, w8.qT, dx8.q, M, K, N, zin=zin, dact=dact, a_scale_inv=dy8.scale_inv, b_scale_inv=w8.scale_inv, c_q8=dx8.c_q8)
             elif dx is not None:
-                ops.gemm(dy8[0], wqT, dx, M, K, N, zin=zin, dact=dact, accumulate=dx_accumulate, a_scale_inv=dy8[1][1:], b_scale_inv=ws[1:])
+                ops.gemm(dy8.q, w8.qT, dx, M, K, N, zin=zin, dact=dact, accumulate=dx_accumulate, a_scale_inv=dy8.scale_inv, b_scale_inv=w8.scale_inv)
             if not defer:
                 self._done(wname + ".w")
             return dx
@@ -488,15 +274,6 @@ class Engine:
         if not defer:
             self._done(wname + ".w")
         return dx
-
-    def dy8_target(self, wname: str, par: int, cap: int):
-        """fused-emission target (see `_q8_target`) for the gradient w.r.t. the OUTPUT of the fp8 Linear `wname` — the e5m2 dy its
-        backward GEMMs read; `par`: layer parity (the deferred weight-gradient launch of a layer reads it while the next layer's
-        backward already writes the other buffer).  None when the Linear is not fp8 / the tensor has no scale history."""
-        if not self._fp8_ok(wname):
-            return None
-        kind = wname.split(".")[0].rstrip("0123456789") + "." + wname.split(".")[-1]
-        return self._q8_target(wname + ".dy", f"f8.{kind}.dy.{par}", cap, self.P.w(wname + ".w").shape[0], torch.float8_e5m2)
 
     def ln_folded(self, wname: str, ln: str):
         """(gamma o W, colsum, bias') of Linear `wname` behind LayerNorm `ln` (mic_ln_fold_weight), rebuilt when the weights
@@ -572,16 +349,12 @@ class Engine:
         side = None
         if self._dw_on():
             if self._dw_stream is None:
-                import os
-
                 n = int(os.environ.get("MIC_DW_CUS", "0"))  # A/B: the weight-gradient stream on the LAST n CUs of the mask only
                 self._dw_stream = ops.cu_masked_stream(256 - n, n, self.dev) if n > 0 else ops.role_stream(self.dev, "dw")
             side = self._dw_stream
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
             side.wait_event(ev)
-        import contextlib
-
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             with (ops.pinned_stream() if side is not None else contextlib.nullcontext()):
                 self._dw_side = side is not None
@@ -656,7 +429,7 @@ class Engine:
             tag = f"v{l}." if save else "v_."
             p = f"vit{l}."
             st1 = self.buf(tag + "st1", 2, _rup(Mv, ROWPAD), torch.float32)
-            a1, a1_8 = self.ln_x8(x, p + "ln1", self.vit_eps, tag + "a1", Mv, st1[0], st1[1], Mv, p + "qkv", tag)
+            a1, a1_8 = self.ln_q8(x, p + "ln1", self.vit_eps, tag + "a1", Mv, st1[0], st1[1], Mv, p + "qkv", tag)
             qkv = self.buf(tag + "qkv", Mv, 3 * vd)
             self.linear(a1, p + "qkv", qkv, Mv, save_tag=tag if save else None, x8=a1_8)
             ctx = self.buf(tag + "ctx", Mv, vd)
@@ -665,10 +438,10 @@ class Engine:
             xm = self.buf(tag + "xm", Mv, vd)
             self.linear(ctx, p + "o", xm, Mv, residual=x)
             st2 = self.buf(tag + "st2", 2, _rup(Mv, ROWPAD), torch.float32)
-            a2, a2_8 = self.ln_x8(xm, p + "ln2", self.vit_eps, tag + "a2", Mv, st2[0], st2[1], Mv, p + "fc1", tag)
+            a2, a2_8 = self.ln_q8(xm, p + "ln2", self.vit_eps, tag + "a2", Mv, st2[0], st2[1], Mv, p + "fc1", tag)
             z = self.buf(tag + "z", Mv, vf)
             # the GELU output's only reader is FFN-out: with a scale history it leaves the FFN-in epilogue as e4m3 bytes
-            u8t = self._q8_target(p + "fc2.x", tag + "fc2.x", Mv, vf, torch.float8_e4m3fn) if self._fp8_ok(p + "fc2") else None
+            u8t = self.f8.target(p + "fc2.x", tag + "fc2.x", Mv, vf, E4M3) if self._fp8_ok(p + "fc2") else None
             u = self.buf(tag + "u", Mv, vf) if u8t is None else None
             u8 = self.linear(a2, p + "fc1", u, Mv, act=L.ACT_QUICK_GELU, zout=z, save_tag=tag if save else None, x8=a2_8, out8=u8t)
             xo = self.buf(f"v{l}.xo" if save else f"v_.xo{l & 1}", Mv, vd)
@@ -693,12 +466,12 @@ class Engine:
         x_last = self.buf(f"v{P.vL - 1}.xo", Mv, vd)
         dx = self.dyb("vb.dx", P.vL - 1, Mv, vd)
         self.linear_bwd("vp", x_last, dehs, Mv, dx=dx)
-        f8 = self.fp8  # fp8 projections: their inputs exist as saved fp8 bytes (Engine._x8); the bf16 names below may hold nothing
-        dx8 = None     # (q, state) of dx when the LayerNorm backward that produced it emitted the e5m2 bytes too
+        fp8 = self.fp8  # fp8 projections: their inputs exist as saved fp8 bytes (Fp8State.saved); the bf16 names below may hold nothing
+        dx8 = None     # the Q8 of dx when the LayerNorm backward that produced it emitted the e5m2 bytes too
         for l in reversed(range(P.vL)):
             tag, p = f"v{l}.", f"vit{l}."
             qkv, ctx, xm = (self.buf(tag + n, Mv, c) for n, c in (("qkv", 3 * vd), ("ctx", vd), ("xm", vd)))
-            a1, a2, u = ((None, None, None) if f8 else (self.buf(tag + "a1", Mv, vd), self.buf(tag + "a2", Mv, vd), self.buf(tag + "u", Mv, vf)))
+            a1, a2, u = ((None, None, None) if fp8 else (self.buf(tag + "a1", Mv, vd), self.buf(tag + "a2", Mv, vd), self.buf(tag + "u", Mv, vf)))
             z = self.buf(tag + "z", Mv, vf)
             st1, st2 = self.buf(tag + "st1", 2, _rup(Mv, ROWPAD), torch.float32), self.buf(tag + "st2", 2, _rup(Mv, ROWPAD), torch.float32)
             lse = self.vec(tag + "lse", B * H * S)
@@ -707,17 +480,17 @@ class Engine:
             dz = self.dyb("vb.dz", l, Mv, vf) if dz8t is None else None
             self.linear_bwd(p + "fc2", u, dx, Mv, dx=dz, zin=z, dact=L.ACT_QUICK_GELU, defer=True, dy8=dx8, dx8=dz8t, par=self._par(l))
             da = self.buf("vb.da", Mv, vd)
-            self.linear_bwd(p + "fc1", a2, dz, Mv, dx=da, defer=True, dy8=None if dz8t is None else (dz8t[0], dz8t[1]), par=self._par(l))
+            self.linear_bwd(p + "fc1", a2, dz, Mv, dx=da, defer=True, dy8=None if dz8t is None else dz8t.q8, par=self._par(l))
             dxm = self.dyb("vb.dxm", l, Mv, vd)
             self.ln_bwd("v2", l, xm, p + "ln2", st2[0], st2[1], da, dxm, Mv, dres=dx)
             dctx = self.buf("vb.dctx", Mv, vd)
             self.linear_bwd(p + "o", ctx, dxm, Mv, dx=dctx, defer=True)
             dq8t = self.dy8_target(p + "qkv", self._par(l), Mv) if S <= 64 else None
             if dq8t is not None:
-                q8 = dq8t[0]
-                ops.attn_bwd_q8(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, dctx, lse, dq8t[2], ops.fp8_out(q8[:, vd:], dq8t[1], dq8t[3][1]), q8[:, 2 * vd:],
+                q8 = dq8t.q
+                ops.attn_bwd_q8(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, dctx, lse, dq8t.out, dq8t.view(q8[:, vd:]).out, q8[:, 2 * vd:],
                                 B, H, S, S, ldq=3 * vd, ldk=3 * vd, ldv=3 * vd, ldo=vd, lddo=vd)
-                self.linear_bwd(p + "qkv", a1, None, Mv, dx=da, defer=True, dy8=(dq8t[0], dq8t[1]), par=self._par(l))
+                self.linear_bwd(p + "qkv", a1, None, Mv, dx=da, defer=True, dy8=dq8t.q8, par=self._par(l))
             else:
                 dqkv = self.dyb("vb.dqkv", l, Mv, 3 * vd)
                 ops.attn_bwd(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, dctx, lse, dqkv, dqkv[:, vd:], dqkv[:, 2 * vd:], B, H, S, S,
@@ -731,8 +504,8 @@ class Engine:
             # ... which the layer below's fc2 backward reads as e5m2: emitted here, beside the bf16 dx the residual path needs
             dx8t = self.dy8_target(f"vit{l - 1}.fc2", self._par(l - 1), Mv) if l > 0 else None
             if dx8t is not None:
-                self.ln_bwd("v1", l, x_in, p + "ln1", st1[0], st1[1], da, dx, Mv, dres=dxm, q8=dx8t[2], q8_of_dx=True)
-                dx8 = (dx8t[0], dx8t[1])
+                self.ln_bwd("v1", l, x_in, p + "ln1", st1[0], st1[1], da, dx, Mv, dres=dxm, q8=dx8t.out, q8_of_dx=True)
+                dx8 = dx8t.q8
             else:
                 self.ln_bwd("v1", l, x_in, p + "ln1", st1[0], st1[1], da, dx, Mv, dres=dxm)
                 dx8 = None
@@ -778,7 +551,7 @@ class Engine:
             tag = f"d{l}." if save else "d_."
             p = f"dec{l}."
             stats = self.buf(tag + "stats", 6, _rup(Mcap, ROWPAD), torch.float32)
-            a, a8 = self.ln_x8(x, p + "ln_sa", self.dec_eps, tag + "a_sa", Mcap, stats[0], stats[1], M, p + "qkv", tag)
+            a, a8 = self.ln_q8(x, p + "ln_sa", self.dec_eps, tag + "a_sa", Mcap, stats[0], stats[1], M, p + "qkv", tag)
             qkv = self.buf(tag + "qkv", Mcap, 3 * d)
             self.linear(a, p + "qkv", qkv, M, save_tag=tag if save else None, x8=a8)
             ctx = self.buf(tag + "ctx", Mcap, d)
@@ -791,7 +564,7 @@ class Engine:
                              causal=True, lse=lse)
             x1 = self.buf(tag + "x1", Mcap, d)
             self.linear(ctx, p + "so", x1, M, residual=x, drop_seed=sd(10 + 3 * l))
-            a, a8 = self.ln_x8(x1, p + "ln_ca", self.dec_eps, tag + "a_ca", Mcap, stats[2], stats[3], M, p + "cq", tag)
+            a, a8 = self.ln_q8(x1, p + "ln_ca", self.dec_eps, tag + "a_ca", Mcap, stats[2], stats[3], M, p + "cq", tag)
             q = self.buf(tag + "cq", Mcap, d)
             self.linear(a, p + "cq", q, M, save_tag=tag if save else None, x8=a8)
             if kvcat is not None:
@@ -808,9 +581,9 @@ class Engine:
                 ops.attn_fwd(q, kv, kv[:, d:], cctx, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lse=clse)
             x2 = self.buf(tag + "x2", Mcap, d)
             self.linear(cctx, p + "co", x2, M, residual=x1, drop_seed=sd(11 + 3 * l))
-            a, a8 = self.ln_x8(x2, p + "ln_ff", self.dec_eps, tag + "a_ff", Mcap, stats[4], stats[5], M, p + "fc1", tag)
+            a, a8 = self.ln_q8(x2, p + "ln_ff", self.dec_eps, tag + "a_ff", Mcap, stats[4], stats[5], M, p + "fc1", tag)
             z = self.buf(tag + "z", Mcap, f)
-            u8t = self._q8_target(p + "fc2.x", tag + "fc2.x", Mcap, f, torch.float8_e4m3fn) if self._fp8_ok(p + "fc2") else None
+            u8t = self.f8.target(p + "fc2.x", tag + "fc2.x", Mcap, f, E4M3) if self._fp8_ok(p + "fc2") else None
             u = self.buf(tag + "u", Mcap, f) if u8t is None else None
             u8 = self.linear(a, p + "fc1", u, M, act=self.gelu, zout=z, save_tag=tag if save else None, x8=a8, out8=u8t)
             x3 = self.buf(f"d{l}.x3" if save else f"d_.x3{l & 1}", Mcap, d)
@@ -836,13 +609,14 @@ class Engine:
         P = self.P
         w, b = P.ckv_cat("w")
         kvcat = self.buf(tag + "ckvcat", Mv, P.L * 2 * P.d)
-        if self.fp8 and "ckvcat" in self._w8:
-            self._w8_wait()
-            wq, _, ws = self._w8["ckvcat"]
-            x8 = self._quant(ehs, Mv, P.d, "ckvcat.x", tag + "ckvcat.x", torch.float8_e4m3fn)
+        if self.fp8 and "ckvcat" in self.f8.weights:
+            f8 = self.f8
+            f8.wait()
+            w8 = f8.weights["ckvcat"]
+            x8 = f8.quant(ehs, Mv, P.d, "ckvcat.x", tag + "ckvcat.x", E4M3)
             if save:
-                self._x8["ckvcat"] = x8
-            ops.gemm(x8[0], wq, kvcat, Mv, P.L * 2 * P.d, P.d, bias=b, a_scale_inv=x8[1][1:], b_scale_inv=ws[1:])
+                f8.saved["ckvcat"] = x8
+            ops.gemm(x8.q, w8.q, kvcat, Mv, P.L * 2 * P.d, P.d, bias=b, a_scale_inv=x8.scale_inv, b_scale_inv=w8.scale_inv)
         else:
             ops.gemm(ehs, w, kvcat, Mv, P.L * 2 * P.d, P.d, bias=b)
         return kvcat
@@ -865,11 +639,12 @@ class Engine:
         MIC_FP8_HEAD=all — the e4m3 copies of both (the quantised hidden states stay for the head's weight gradient)"""
         P = self.P
         if fp8 and self._head8() and self.fp8_head == 2:
-            x8 = self._head_x8 = self._quant(hf, M, P.d, "head.x", "head.x", torch.float8_e4m3fn)
-            E8, _, wst = self._w8["shared"]
-            self._w8_wait()
-            ops.gemm(x8[0], E8, logits, M, P.Vpad, P.d, bias=P.f32("flb"), rowstat=stat, rowstat_nvalid=P.V,
-                     a_scale_inv=x8[1][1:], b_scale_inv=wst[1:])
+            f8 = self.f8
+            x8 = f8.head_x = f8.quant(hf, M, P.d, "head.x", "head.x", E4M3)
+            E8 = f8.weights["shared"]
+            f8.wait()
+            ops.gemm(x8.q, E8.q, logits, M, P.Vpad, P.d, bias=P.f32("flb"), rowstat=stat, rowstat_nvalid=P.V,
+                     a_scale_inv=x8.scale_inv, b_scale_inv=E8.scale_inv)
         else:
             ops.gemm(hf, P.w("shared"), logits, M, P.Vpad, P.d, bias=P.f32("flb"), rowstat=stat, rowstat_nvalid=P.V)
 
@@ -902,13 +677,17 @@ class Engine:
         Mhp = _rup(Mh, 64)
         nt = self._head_nt_state
         self._head_nt_state = None
-        h8s, self._head8_state = self._head8_state, None
+        f8 = self.f8 if self.fp8 else None
+        h8s = None
+        if f8 is not None:
+            h8s, f8.head_dy = f8.head_dy, None
         if h8s is not None:
+            dl8, coef, labels = h8s
             # fp8 head: dE = dlogits^T . h over K = rows, both operands k-major (the e5m2 copy of dlogits as the CE backward wrote it,
             # the e4m3 hidden states; rows >= Mh of the 128-row reduction padding count as zero), fp32 straight into the gradient buffer
-            x8 = self._head_x8 or self._quant(hf, Mh, d, "head.x", "head.x", torch.float8_e4m3fn)
-            ops.gemm(h8s[0], x8[0], P.g("shared"), P.Vpad, d, _rup(Mh, 128), a_kmajor=True, b_kmajor=True, k_valid=Mh,
-                     a_scale_inv=h8s[1][1:], b_scale_inv=x8[1][1:])
+            x8 = f8.head_x or f8.quant(hf, Mh, d, "head.x", "head.x", E4M3)
+            ops.gemm(dl8.q, x8.q, P.g("shared"), P.Vpad, d, _rup(Mh, 128), a_kmajor=True, b_kmajor=True, k_valid=Mh,
+                     a_scale_inv=dl8.scale_inv, b_scale_inv=x8.scale_inv)
             # the label entries (kept out of the byte matrix): + coef h into dE's label rows, coef E[label] as one more slab of dX
             tiles = ((Mh + 255) // 256) * ((d + 255) // 256)
             nsp = max(1, min(ops.get_cu_budget() // tiles, P.Vpad // 128 // 2))
@@ -916,7 +695,7 @@ class Engine:
             cap_rows = max(_rup(Mcap, 256), (256 // max(1, (d + 255) // 256)) * 256) + _rup(Mcap, 256)
             d32 = self.buf("db.dhf32", cap_rows, d, torch.float32)
             assert (nsp + 1) * slab_rows <= d32.shape[0], (nsp, slab_rows, d32.shape)
-            ops.head_label_terms(h8s[3], h8s[2], P.w("shared"), hf, d32[nsp * slab_rows:], P.g("shared"), Mh, d)
+            ops.head_label_terms(labels, coef, P.w("shared"), hf, d32[nsp * slab_rows:], P.g("shared"), Mh, d)
         elif nt is not None:
             # NT launches on the four-wave kernel: dE = dlogits^T . (h^T)^T over K = rows (zero-padded to a multiple of 128 by the CE
             # backward; the bias gradient was summed there), fp32 straight into the gradient buffer
@@ -938,10 +717,10 @@ class Engine:
         if h8s is not None:
             # dX = dlogits . (E^T)^T over K = Vpad on the e5m2 / e4m3 copies, split over K as below; the slabs and the label slab are
             # summed and rounded to bf16 once
-            _, ET8, wst = self._w8["shared"]
-            self._w8_wait()
+            E8 = f8.weights["shared"]
+            f8.wait()
             slab = slab_rows * d
-            ops.gemm(h8s[0], ET8, d32, Mh, d, P.Vpad, split_k=nsp, split_stride=slab if nsp > 1 else 0, a_scale_inv=h8s[1][1:], b_scale_inv=wst[1:])
+            ops.gemm(dl8.q, E8.qT, d32, Mh, d, P.Vpad, split_k=nsp, split_stride=slab if nsp > 1 else 0, a_scale_inv=dl8.scale_inv, b_scale_inv=E8.scale_inv)
             ops.sum_slabs(d32, nsp + 1, slab, dhc, Mh, d, d32.stride(0), dhc.stride(0))
         elif nt is not None:
             # dX = dlogits . (E^T)^T over K = Vpad: ceil(Mh / 256) x d / 256 output tiles, split over K so that one round of blocks
@@ -985,15 +764,14 @@ class Engine:
         dxm8t = self.dy8_target(f"dec{P.L - 1}.fc2", self._par(P.L - 1), Mcap)
         dxm = self.dyb("db.dxm_a", P.L - 1, Mcap, d) if dxm8t is None else None
         self.ln_bwd("f", 0, x_last, "dec.ln_f", stf[0], stf[1], dhf, dx, M, dxm=dxm, dropout_p=pd, dropout_seed=sd(12 + 3 * (P.L - 1)),
-                    **({} if dxm8t is None else dict(q8=dxm8t[2])))
-        dxm8 = None if dxm8t is None else (dxm8t[0], dxm8t[1])
-        f8 = self.fp8
+                    **({} if dxm8t is None else dict(q8=dxm8t.out)))
+        dxm8 = None if dxm8t is None else dxm8t.q8
         dehs = self.buf("db.dehs", Mv, d)
         hoist = self.ckv_hoisted()
         kvcat = self.buf("d.ckvcat", Mv, P.L * 2 * d) if hoist else None
-        hoist8 = hoist and self.fp8 and "ckvcat" in self._w8
+        hoist8 = hoist and f8 is not None and "ckvcat" in f8.weights
         # fp8, hoisted: every layer's dK | dV lands in its column slice of ONE e5m2 matrix under one scale (fused emission) ...
-        dkvcat8t = self._q8_target("ckvcat.dy", "f8.ckvcat.dy", Mv, P.L * 2 * d, torch.float8_e5m2) if (hoist8 and T <= 64 and S <= 64) else None
+        dkvcat8t = f8.target("ckvcat.dy", "f8.ckvcat.dy", Mv, P.L * 2 * d, E5M2) if (hoist8 and T <= 64 and S <= 64) else None
         # ... or, without a scale history, in the bf16 matrix that is quantised once behind the loop
         dkvcat = self.buf("db.dkvcat", Mv, P.L * 2 * d) if (hoist and dkvcat8t is None) else None
         for l in reversed(range(P.L)):
@@ -1003,8 +781,8 @@ class Engine:
             cq, cctx, x2 = (self.buf(tag + n, Mcap, d) for n in ("cq", "cctx", "x2"))
             ckv, ldkv = (kvcat[:, l * 2 * d:], kvcat.stride(0)) if hoist else (self.buf(tag + "ckv", Mv, 2 * d), 2 * d)
             z = self.buf(tag + "z", Mcap, f)
-            # (fp8 projections read their saved fp8 inputs, Engine._x8: the bf16 copies need not exist)
-            a_sa, a_ca, a_ff, u = (None,) * 4 if f8 else (self.buf(tag + "a_sa", Mcap, d), self.buf(tag + "a_ca", Mcap, d),
+            # (fp8 projections read their saved fp8 inputs, Fp8State.saved: the bf16 copies need not exist)
+            a_sa, a_ca, a_ff, u = (None,) * 4 if f8 is not None else (self.buf(tag + "a_sa", Mcap, d), self.buf(tag + "a_ca", Mcap, d),
                                                           self.buf(tag + "a_ff", Mcap, d), self.buf(tag + "u", Mcap, f))
             lse, clse = self.vec(tag + "lse", B * H * T), self.vec(tag + "clse", B * H * T)
             x_in = self.buf(f"d{l - 1}.x3", Mcap, d) if l > 0 else self.buf("d.x0", Mcap, d)
@@ -1014,7 +792,7 @@ class Engine:
             dz = self.dyb("db.dz", l, Mcap, f) if dz8t is None else None
             self.linear_bwd(p + "fc2", u, dxm, M, dx=dz, zin=z, dact=self.gelu, defer=True, dy8=dxm8, dx8=dz8t, par=self._par(l))
             da = self.buf("db.da", Mcap, d)
-            self.linear_bwd(p + "fc1", a_ff, dz, M, dx=da, defer=True, dy8=None if dz8t is None else (dz8t[0], dz8t[1]), par=self._par(l))
+            self.linear_bwd(p + "fc1", a_ff, dz, M, dx=da, defer=True, dy8=None if dz8t is None else dz8t.q8, par=self._par(l))
             dx2 = self.buf("db.dx2", Mcap, d)
             self.ln_bwd("ff", l, x2, p + "ln_ff", stats[4], stats[5], da, dx2, M,
                         dres=dx, dxm=dxm_b, dropout_p=pd, dropout_seed=sd(11 + 3 * l))
@@ -1024,17 +802,16 @@ class Engine:
             one_tile = T <= 64 and S <= 64
             dq8t = self.dy8_target(p + "cq", self._par(l), Mcap) if one_tile else None
             if hoist:
-                kv8 = None if dkvcat8t is None else dkvcat8t[0][:, l * 2 * d:]
-                dkv8t = None if kv8 is None else (kv8, dkvcat8t[1], ops.fp8_out(kv8, dkvcat8t[1], dkvcat8t[3][1]))
+                dkv8t = None if dkvcat8t is None else dkvcat8t.view(dkvcat8t.q[:, l * 2 * d:])
             else:
                 dkv8t = self.dy8_target(p + "ckv", self._par(l), Mv) if one_tile else None
             if dq8t is not None and dkv8t is not None:
                 # dQ [rows][d] and dK | dV [encoder rows][2d] as e5m2 bytes under their own scales, straight out of the attention backward
-                ops.attn_bwd_q8(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq8t[2], dkv8t[2], dkv8t[0][:, d:], B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv,
+                ops.attn_bwd_q8(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq8t.out, dkv8t.out, dkv8t.q[:, d:], B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv,
                                 ldo=d, lddo=d, q_off=pack[0] if pack is not None else None, q_len=pack[1] if pack is not None else None, kv_packed=False)
-                self.linear_bwd(p + "cq", a_ca, None, M, dx=da, defer=True, dy8=(dq8t[0], dq8t[1]), par=self._par(l))
+                self.linear_bwd(p + "cq", a_ca, None, M, dx=da, defer=True, dy8=dq8t.q8, par=self._par(l))
                 if not hoist:
-                    self.linear_bwd(p + "ckv", ehs, None, Mv, dx=dehs, dx_accumulate=(l != P.L - 1), defer=True, dy8=(dkv8t[0], dkv8t[1]), par=self._par(l))
+                    self.linear_bwd(p + "ckv", ehs, None, Mv, dx=dehs, dx_accumulate=(l != P.L - 1), defer=True, dy8=dkv8t.q8, par=self._par(l))
             elif hoist and dkvcat8t is not None:
                 # (dQ has no scale history yet but the concatenated k/v gradient has: cannot happen after the first pass; keep the bytes consistent)
                 raise RuntimeError("fp8: cross-attention dQ without a scale history beside a hoisted k/v gradient with one")
@@ -1057,12 +834,12 @@ class Engine:
             self.linear_bwd(p + "so", ctx, dxm_c, M, dx=dctx, defer=True)
             dqkv8t = self.dy8_target(p + "qkv", self._par(l), Mcap) if T <= 64 else None
             if dqkv8t is not None:
-                q8 = dqkv8t[0]
-                ops.attn_bwd_q8(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv8t[2], ops.fp8_out(q8[:, d:], dqkv8t[1], dqkv8t[3][1]), q8[:, 2 * d:],
+                q8 = dqkv8t.q
+                ops.attn_bwd_q8(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv8t.out, dqkv8t.view(q8[:, d:]).out, q8[:, 2 * d:],
                                 B, H, T, T, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, q_off=pack[0] if pack is not None else None,
                                 q_len=pack[1] if pack is not None else None, kv_packed=pack is not None,
                                 key_mask=key_mask if pack is None else None, causal=True)
-                self.linear_bwd(p + "qkv", a_sa, None, M, dx=da, defer=True, dy8=(dqkv8t[0], dqkv8t[1]), par=self._par(l))
+                self.linear_bwd(p + "qkv", a_sa, None, M, dx=da, defer=True, dy8=dqkv8t.q8, par=self._par(l))
             else:
                 dqkv = self.dyb("db.dqkv", l, Mcap, 3 * d)
                 if pack is not None:
@@ -1081,8 +858,8 @@ class Engine:
                 dxm8t = self.dy8_target(f"dec{l - 1}.fc2", self._par(l - 1), Mcap)
                 dxm = self.dyb("db.dxm_a", l - 1, Mcap, d) if dxm8t is None else None
                 self.ln_bwd("sa", l, x_in, p + "ln_sa", stats[0], stats[1], da, dx, M, dres=dx1, dxm=dxm, dropout_p=pd,
-                            dropout_seed=sd(12 + 3 * (l - 1)), **({} if dxm8t is None else dict(q8=dxm8t[2])))
-                dxm8 = None if dxm8t is None else (dxm8t[0], dxm8t[1])
+                            dropout_seed=sd(12 + 3 * (l - 1)), **({} if dxm8t is None else dict(q8=dxm8t.out)))
+                dxm8 = None if dxm8t is None else dxm8t.q8
             else:
                 self.ln_bwd("sa", l, x_in, p + "ln_sa", stats[0], stats[1], da, dx, M, dres=dx1)
             if flush_now and late:
@@ -1096,22 +873,22 @@ class Engine:
             N = P.L * 2 * d
             Mvp = _rup(Mv, ROWPAD)
             if hoist8:
-                dkv8 = (dkvcat8t[0], dkvcat8t[1]) if dkvcat8t is not None else self._quant(dkvcat, Mv, N, "ckvcat.dy", "f8.ckvcat.dy", torch.float8_e5m2)
-                x8 = self._x8.get("ckvcat")
+                dkv8 = dkvcat8t.q8 if dkvcat8t is not None else f8.quant(dkvcat, Mv, N, "ckvcat.dy", "f8.ckvcat.dy", E5M2)
+                x8 = f8.saved.get("ckvcat")
                 if x8 is None:
                     raise RuntimeError("fp8 backward of the hoisted cross k/v projection: the forward pass did not keep the fp8 encoder states")
-                _, wqT, ws = self._w8["ckvcat"]
+                w8 = f8.weights["ckvcat"]
                 nsp = min(8, N // 128)
                 if nsp > 1:
                     slab = Mvp * d
                     d32 = self.buf("db.dehs32", nsp * Mvp, d, torch.float32)
-                    ops.gemm(dkv8[0], wqT, d32, Mv, d, N, split_k=nsp, split_stride=slab, a_scale_inv=dkv8[1][1:], b_scale_inv=ws[1:])
+                    ops.gemm(dkv8.q, w8.qT, d32, Mv, d, N, split_k=nsp, split_stride=slab, a_scale_inv=dkv8.scale_inv, b_scale_inv=w8.scale_inv)
                     ops.sum_slabs(d32, nsp, slab, dehs, Mv, d, d32.stride(0), dehs.stride(0))
                 else:
-                    ops.gemm(dkv8[0], wqT, dehs, Mv, d, N, a_scale_inv=dkv8[1][1:], b_scale_inv=ws[1:])
-                self._dw8_queue.append((ops.gemm_args(dkv8[0], x8[0], gw, N, d, Mvp, a_kmajor=True, b_kmajor=True, k_valid=Mv,
-                                                      a_scale_inv=dkv8[1][1:], b_scale_inv=x8[1][1:]), f"dec{P.L - 1}.ckv", True))
-                self._cs8_queue.append((dkv8[0], gb, dkv8[1][1:], Mv, N))
+                    ops.gemm(dkv8.q, w8.qT, dehs, Mv, d, N, a_scale_inv=dkv8.scale_inv, b_scale_inv=w8.scale_inv)
+                self._dw8_queue.append((ops.gemm_args(dkv8.q, x8.q, gw, N, d, Mvp, a_kmajor=True, b_kmajor=True, k_valid=Mv,
+                                                      a_scale_inv=dkv8.scale_inv, b_scale_inv=x8.scale_inv), f"dec{P.L - 1}.ckv", True))
+                self._cs8_queue.append((dkv8.q, gb, dkv8.scale_inv, Mv, N))
                 self._ckv_block_name = f"dec{P.L - 1}.ckv"
                 try:
                     self.flush_dw()
@@ -1182,14 +959,14 @@ class Engine:
         if backward and self._head8():
             # fp8 head: dlogits leave as ONE e5m2 copy (the logits stay) under the scale this tensor has in closed form (mic_ce_bwd_q8)
             ops.zero(P.g("flb"))
-            q = self.buf("head.dl.q8", logits.shape[0], P.Vpad, torch.float8_e5m2)
+            q = self.buf("head.dl.q8", logits.shape[0], P.Vpad, E5M2)
             st = self.vec("head.dl.state", 2)
             # ... except the label entry of every row (at least half of the row's gradient energy): an fp32 coefficient whose two
             # products decoder_backward adds exactly (mic_head_label_terms)
             coef = self.vec("head.dl.coef", _rup(logits.shape[0], ROWPAD))
             ops.ce_bwd_q8(logits, logits.stride(0), P.V, P.Vpad, labels, mask, label_smoothing, lse, denom, M, ops.fp8_out(q, st), colsum=P.g("flb"),
                           label_coef=coef)
-            self._head8_state = (q, st, coef, labels)
+            self.f8.head_dy = (Q8(q, st), coef, labels)
             self._head_nt_state = None
         elif backward:
             kcap = self._head_nt_kcap(logits)

@@ -130,13 +130,13 @@ class FlaxCLIPVisionMBartPreTrainedModel(FlaxCLIPVisionMBartGenerationMixin):
         self.store.load_flat(flat)
         self._params_cache = params
         if self.engine.fp8:
-            self.engine.fp8_weights_changed()
+            self.engine.f8.weights_changed()
 
     def invalidate_params_cache(self, by_optimizer: bool = False):
         self._params_cache = None
         self.store.version = getattr(self.store, "version", 0) + 1
         if self.engine.fp8:
-            self.engine.fp8_weights_changed(by_optimizer=by_optimizer)
+            self.engine.f8.weights_changed(by_optimizer=by_optimizer)
 
     def _use_params(self, params):
         if params is not None and params is not self._params_cache:

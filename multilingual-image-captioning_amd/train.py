@@ -542,7 +542,6 @@ class Trainer:
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.group = group
         self.seed = seed
-        self.dropout_seed = (seed * 1000003 + self.rank * 7919) & 0xFFFFFFFF  # per-device dropout stream (main.py:251)
         st = model.store
         st.ensure_grads()
         st.ensure_opt_state()
@@ -623,6 +622,7 @@ class Trainer:
         self._gscale = 1.0 / self.world
         self._use_acc = False  # True while the optimizer passes of an accumulation's last micro-step are issued (world 1: AdamW on g + acc)
         self._micro = 0        # micro-steps taken since the last optimizer step
+        self._loss_sum = None  # accumulation: the sum of their losses (device scalar)
         if self.accumulate_steps > 1:
             st.ensure_grad_acc()
             self._gscale = 1.0 / (self.world * self.accumulate_steps)
@@ -631,7 +631,6 @@ class Trainer:
             self._when_acc = ["end" if (b < sh.offset + sh.numel and e > sh.offset) else "exchanged" for (b, e) in self.buckets]
             self._acc_cb = lambda b, e: me()._accumulate_slice(b, e)
             self._pre_cb = lambda b, e: me()._add_acc_slice(b, e)
-            self._loss_sum = None
 
     def _adamw_slice(self, b: int, e: int):
         """AdamW on flat slice [b, e) — runs on the reducer's side stream right after that bucket's all-reduce.  The part of the
@@ -643,7 +642,6 @@ class Trainer:
         if not self._split_shared or lo >= hi:
             ops.adamw(st.master[b:e], st.m[b:e], st.v[b:e], st.grad[b:e], None if st.lp is st.master else st.lp[b:e], self.hyper,
                       self.b1, self.b2, self.eps, self.wd, grad_scale=self._gscale, n=e - b, acc=st.acc[b:e] if self._use_acc else None)
-            self.model.engine.fp8_requantize_range(b, e)  # fp8 GEMMs: the bucket's weights as fp8 for the NEXT step, here under backward
             return
         assert (lo - sb) % width == 0 and (hi - sb) % width == 0, "bucket cuts inside the tied embedding are row-aligned"
         for (x, y) in ((b, lo), (hi, e)):
@@ -651,7 +649,6 @@ class Trainer:
                 ops.adamw(st.master[x:y], st.m[x:y], st.v[x:y], st.grad[x:y], None if st.lp is st.master else st.lp[x:y], self.hyper,
                           self.b1, self.b2, self.eps, self.wd, grad_scale=self._gscale, n=y - x, acc=st.acc[x:y] if self._use_acc else None)
         self._adamw_shared(0, (lo - sb) // width, (hi - sb) // width)
-        self.model.engine.fp8_requantize_range(b, e)
 
     def _adamw_shared(self, want: int, r0: int = 0, r1: Optional[int] = None):
         """AdamW on rows [r0, r1) of the tied embedding whose flag equals `want`"""
@@ -698,8 +695,8 @@ class Trainer:
             for held in (r._pending, r._at_end):
                 if held:
                     upto = min(upto, min(h[0] for h in held))
-            if upto > 0:
-                self.model.engine.fp8_refresh_weights(ops.role_stream(self.model.device, "aux"), upto=upto, wait_event=ev2)
+            if upto > 0 and self.model.engine.f8 is not None:
+                self.model.engine.f8.refresh_weights(ops.role_stream(self.model.device, "aux"), upto=upto, wait_event=ev2)
 
     def _flag_embedding_rows(self, ids: torch.Tensor):
         """flags the rows of `shared` that this step's decoder input ids (of every rank) will add a sparse gradient to"""
@@ -802,98 +799,54 @@ class Trainer:
         try:
             ms = self.reducer.step_stream
             if ms is None:
-                return self._train_step(batch)
+                return self._step(batch)
             # the optimizer's stream carries a CU mask, which makes it a blocking stream: the step keeps off the null stream
             cur = torch.cuda.current_stream()
             ms.wait_stream(cur)
             with torch.cuda.stream(ms):
-                out = self._train_step(batch)
+                out = self._step(batch)
             cur.wait_stream(ms)
             return out
         finally:
             if budget:
                 ops.set_cu_budget(0)  # generation / evaluation have no collective beside them
 
-    def _train_step(self, batch: Dict) -> Dict[str, float]:
-        if self.accumulate_steps > 1:
-            return self._micro_step(batch)
-        m, st, eng = self.model, self.model.store, self.model.engine
-        px, labels, mask, dec_in, pos, B, T = self._prep(batch)
-        seed = (self.dropout_seed + self.step * 0x9E3779B1) & 0xFFFFFFFF  # split(dropout_rng) per step (main.py:686)
-        lr = float(self.lr_fn(self.step))  # schedule at the pre-increment count, bias correction with count+1
-        self._set_hyper(lr, float(self.step + 1))
-        self.reducer.start_step()
-        eng.grad_progress = self.reducer.progress if self.reducer.active else None
-        eng.defer_embed = self.world > 1
-        # single process: the flagged rows of the tied embedding get their optimizer pass as soon as decoder backward has scattered the
-        # input-embedding rows into them — under the ViT's backward instead of behind the step (0.09 ms + a stream hand-over)
-        self._late_done = False
-        eng.on_embed_rows = self._embed_rows_done if (self.world == 1 and self._split_shared and self.reducer.on_ready is not None
-                                                      and self._late_early) else None
-        with ops.pinned_stream():
-            if self._split_shared:
-                self._flag_embedding_rows(self._pack[1] if self._pack is not None else dec_in.reshape(-1))
-            if self._pack is not None:  # the decoder sees the valid positions only
-                pack, ids_p, pos_p = self._pack
-                loss = eng.loss_and_grads(px, ids_p, pos_p, None, labels.reshape(-1), B, T, label_smoothing=self.ls, seed=seed,
-                                          rows=self._rows, row_labels=self._row_labels, pack=pack)
-            else:
-                loss = eng.loss_and_grads(px, dec_in.reshape(-1), pos.reshape(-1), mask, labels.reshape(-1), B, T,
-                                          label_smoothing=self.ls, seed=seed, rows=self._rows, row_labels=self._row_labels)
-        # pmean(grad) (main.py:698): SUM here, 1/world folded into AdamW's grad_scale.  The remaining buckets go out; behind them the
-        # sparse embedding-row exchange, the optimizer passes that had to wait for it, and the flagged rows of the tied embedding
-        eng.on_embed_rows = None
-        self.reducer.finish(before=self._scatter_embedding_rows if self.world > 1 else None,
-                            after=self._adamw_shared_late if (self._split_shared and not self._late_done) else None)
-        if not self.overlap_optimizer:
-            ops.adamw(st.master, st.m, st.v, st.grad, None if st.lp is st.master else st.lp, self.hyper, self.b1, self.b2, self.eps,
-                      self.wd, grad_scale=self._gscale)
-            eng.fp8_requantize_range(0, st.numel)
-        m.invalidate_params_cache(by_optimizer=True)
-        if m.device.type == "cuda":
-            eng.fp8_refresh_weights(ops.role_stream(m.device, "aux"))  # fp8 GEMMs: next step's weight copies, beside the glue between the steps
-            # the k-contiguous copy of the tied embedding for the NEXT step's head backward: behind this step's optimizer passes, on a
-            # stream of its own — it has the whole next forward pass to finish (engine.shared_T waits for it)
-            eng.refresh_shared_T(ops.role_stream(m.device, "aux"), st.version)
-        self.step += 1
-        if self.world == 1:
-            # one launch instead of three (two copies + a clone) in the gap between two steps; fresh storage per step (callers keep these)
-            out = torch.cat((loss.reshape(1), self.hyper[0:1]))
-            return {"loss": out[0], "learning_rate": out[1]}
-        self.metrics_buf[0:1].copy_(loss)
-        self.metrics_buf[1:2].copy_(self.hyper[0:1])  # lr, device to device (a Python scalar assigned into a device tensor syncs)
-        return self._pmean_metrics()
-
-    def _micro_step(self, batch: Dict) -> Dict[str, float]:
-        """`train_step` under accumulate_steps = N > 1: micro-step j = self._micro of the pending optimizer step.  j < N - 1: backward
-        into `grad`, then `acc (+)= grad` — per bucket on the optimizer stream as backward reports it, no exchange, no optimizer, the
-        weights untouched.  j = N - 1: the step of `_train_step` on grad + acc with grad_scale 1 / (world * N)."""
+    def _step(self, batch: Dict) -> Dict[str, float]:
+        """One `train_step` call = micro-step j = self._micro of the pending optimizer step under accumulate_steps = N (N = 1: the step
+        itself).  j < N - 1: backward into `grad`, then `acc (+)= grad` — per bucket on the optimizer stream as backward reports it, no
+        exchange, no optimizer, the weights untouched.  j = N - 1: the optimizer step (main.py:684-707), for N > 1 on grad + acc, with
+        grad_scale 1 / (world * N)."""
         m, st, eng = self.model, self.model.store, self.model.engine
         N, j = self.accumulate_steps, self._micro
         final = j == N - 1
         px, labels, mask, dec_in, pos, B, T = self._prep(batch)
-        seed = virtual_rank_dropout_seed(self.seed, self.rank, self.step, N, j)
-        if j == 0:  # (lr, count) of the pending optimizer step: AdamW reads them on the last micro-step, the metrics on every one
+        seed = virtual_rank_dropout_seed(self.seed, self.rank, self.step, N, j)  # split(dropout_rng) per step (main.py:686)
+        if j == 0:
+            # (lr, count) of the pending optimizer step — the schedule at the pre-increment count, bias correction with count+1 (SURVEY
+            # B10): AdamW reads them on the last micro-step, the metrics on every one
             self._set_hyper(float(self.lr_fn(self.step)), float(self.step + 1))
         r = self.reducer
         per_bucket = r.on_ready is not None
         if final:
-            # one rank: every AdamW launch reads g + acc.  Several: the sum joins the gradient in front of each all-reduce, AdamW is the plain one
-            self._use_acc = self.world == 1
-            r.start_step(pre_exchange=self._pre_cb if self.world > 1 else None)
+            # accumulation, one rank: every AdamW launch reads g + acc.  Several: the sum joins the gradient in front of each all-reduce,
+            # AdamW is the plain one
+            self._use_acc = N > 1 and self.world == 1
+            r.start_step(pre_exchange=self._pre_cb if (N > 1 and self.world > 1) else None)
         else:
             r.start_step(local=True, on_ready=self._acc_cb if per_bucket else None, ready_when=self._when_acc)
         eng.grad_progress = r.progress if r.active else None
         # the sparse input-embedding rows: scattered locally while accumulating (acc carries them), exchanged on the last micro-step
         eng.defer_embed = final and self.world > 1
+        # single process: the flagged rows of the tied embedding get their optimizer pass as soon as decoder backward has scattered the
+        # input-embedding rows into them — under the ViT's backward instead of behind the step (0.09 ms + a stream hand-over)
         self._late_done = False
         eng.on_embed_rows = self._embed_rows_done if (final and self.world == 1 and self._split_shared and per_bucket
                                                       and self._late_early) else None
         try:
             with ops.pinned_stream():
-                if final and self._split_shared:  # the rows of THIS micro-step's ids only: acc is already complete for every row
+                if final and self._split_shared:  # (accumulation: the rows of THIS micro-step's ids only — acc is already complete for every row)
                     self._flag_embedding_rows(self._pack[1] if self._pack is not None else dec_in.reshape(-1))
-                if self._pack is not None:
+                if self._pack is not None:  # the decoder sees the valid positions only
                     pack, ids_p, pos_p = self._pack
                     loss = eng.loss_and_grads(px, ids_p, pos_p, None, labels.reshape(-1), B, T, label_smoothing=self.ls, seed=seed,
                                               rows=self._rows, row_labels=self._row_labels, pack=pack)
@@ -909,26 +862,40 @@ class Trainer:
                 self._micro = j + 1
                 out = torch.cat((loss.reshape(1), self.hyper[0:1]))
                 return {"loss": out[0], "learning_rate": out[1]}
+            # pmean(grad) (main.py:698): SUM here, 1/world folded into AdamW's grad_scale.  The remaining buckets go out; behind them the
+            # sparse embedding-row exchange, the optimizer passes that had to wait for it, and the flagged rows of the tied embedding
             r.finish(before=self._scatter_embedding_rows if self.world > 1 else None,
                      after=self._adamw_shared_late if (self._split_shared and not self._late_done) else None)
             if not self.overlap_optimizer:
                 ops.adamw(st.master, st.m, st.v, st.grad, None if st.lp is st.master else st.lp, self.hyper, self.b1, self.b2, self.eps,
                           self.wd, grad_scale=self._gscale, acc=st.acc if self._use_acc else None)
+            m.invalidate_params_cache(by_optimizer=True)
+            if m.device.type == "cuda":
+                aux = ops.role_stream(m.device, "aux")
+                if eng.f8 is not None:
+                    eng.f8.refresh_weights(aux)  # fp8 GEMMs: next step's weight copies, beside the glue between the steps
+                # the k-contiguous copy of the tied embedding for the NEXT step's head backward: behind this step's optimizer passes, on a
+                # stream of its own — it has the whole next forward pass to finish (engine.shared_T waits for it)
+                eng.refresh_shared_T(aux, st.version)
+        except BaseException:
+            # a step that raised: some optimizer passes may have run, a refresh of the fp8 weight copies may be under way — the next pass
+            # waits for it and re-makes them all from the weights as they are, their scale history restarted (Fp8State)
+            if eng.f8 is not None:
+                eng.f8.weights_changed()
+            raise
         finally:
-            eng.on_embed_rows = None
-            self._use_acc = False
-        m.invalidate_params_cache(by_optimizer=True)
-        if m.device.type == "cuda":
-            eng.refresh_shared_T(ops.role_stream(m.device, "aux"), st.version)
+            eng.on_embed_rows, eng.grad_progress, self._use_acc = None, None, False  # (whatever happened: no hooks into this Trainer stay behind)
         self.step += 1
         self._micro = 0
-        mean = (self._loss_sum + loss.reshape(1)) * (1.0 / N)  # the reference's pmean'd loss over the N virtual ranks; stays on the device
+        # accumulation: the reference's pmean'd loss over the N virtual ranks; stays on the device
+        mean = loss.reshape(1) if N == 1 else (self._loss_sum + loss.reshape(1)) * (1.0 / N)
         self._loss_sum = None
         if self.world == 1:
+            # one launch instead of three (two copies + a clone) in the gap between two steps; fresh storage per step (callers keep these)
             out = torch.cat((mean, self.hyper[0:1]))
             return {"loss": out[0], "learning_rate": out[1]}
         self.metrics_buf[0:1].copy_(mean)
-        self.metrics_buf[1:2].copy_(self.hyper[0:1])
+        self.metrics_buf[1:2].copy_(self.hyper[0:1])  # lr, device to device (a Python scalar assigned into a device tensor syncs)
         return self._pmean_metrics()
 
     def eval_step(self, batch: Dict) -> Dict[str, float]:
