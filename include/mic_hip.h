@@ -495,6 +495,9 @@ int mic_adamw_rows_acc(int64_t rows, int width, const uint8_t* row_flag, int wan
  *       processed log-probs (forced_token >= 0: everything -inf except forced_token := 0; min-length: eos := -inf
  *       when suppress_eos), plus row_bias[row] (the beam's running score, gen:857) — candidates ordered
  *       (value desc, index asc), i.e. lax.top_k (gen:850-873).  raw_logits = 1: no log-softmax (greedy, gen:497-499).
+ *       raw_logits with k = 1 is the greedy argmax: the first maximum of the logits themselves, returned as logit + row_bias
+ *       (every other case orders by the fp32 processed value, ties to the lower index).
+ *       Like lax.top_k, k > V is refused (so is forced_token >= V) and nothing is written: every index that comes back is < V.
  *   mic_beam_step: the whole bookkeeping of one beam_search_body_fn iteration (gen:857-966) per batch item.
  *   mic_greedy_step: argmax + EOS->PAD substitution + append (gen:499-512).
  * ------------------------------------------------------------------------------------------- */
@@ -504,7 +507,7 @@ int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int ld, int k,
 
 /* mic_row_lse_topk's results (no forced token) from the head GEMM's per-granule partials: lse by merging ceil(V / 64) pairs, the
  * top-k by scanning only the 64-column granules whose maximum reaches the k-th largest granule maximum (gen:850-873 without
- * streaming the row) */
+ * streaming the row); k <= 16, k <= V (k > V is refused, nothing is written), V <= 262144, stat_ld >= ceil(V / 64) */
 int mic_row_topk_tiles(int dtype, int R, int V, const void* logits, int ld, const float* rowstat, int stat_ld, int k,
                        int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
                        int32_t* top_idx, void* stream);
@@ -554,7 +557,9 @@ int mic_greedy_step(int B, int max_len, int cur_len, int eos_token_id, int pad_t
  *   min_keep / tie_limit (optional, [R], from mic_warp_thresholds): keep v > min_keep[row], or v == min_keep[row] and
  *   index < tie_limit[row]; everything else is masked.
  * mic_warp_thresholds: FlaxTopKLogitsWarper / FlaxTopPLogitsWarper (gen:338-366; temperature and MinLength applied first)
- *   as a per-row (threshold value, tie index limit) pair: top_k <= 0 disables top-k, top_p >= 1 disables top-p. */
+ *   as a per-row (threshold value, tie index limit) pair: top_k <= 0 disables top-k, top_p >= 1 disables top-p.
+ *   Both entry points compare the scaled logits with -0 read as +0 (thr is never -0), refuse ld < V, and mic_sample_rows refuses
+ *   forced_token >= V. */
 int mic_sample_rows(int dtype, int R, int V, const void* logits, int ld, uint32_t key0, uint32_t key1,
                     float temperature, int forced_token, int suppress_eos, int eos_token_id, const float* min_keep,
                     const int32_t* tie_limit, int32_t* out_idx, void* stream);

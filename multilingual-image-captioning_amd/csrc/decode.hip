@@ -198,6 +198,8 @@ extern "C" int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int
                                 int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
                                 int32_t* top_idx, void* stream) {
   MIC_CHECK(R > 0 && V > 0 && ld >= V && ld % 8 == 0 && k >= 1 && k <= TOPK_WIDE && logits && top_val && top_idx, "mic_row_lse_topk: bad args (k <= 64)");
+  // lax.top_k refuses k > V; the unfilled slots would come back as (-inf, 0x7fffffff) and flow into next_token
+  MIC_CHECK(k <= V && forced_token < V, "mic_row_lse_topk: k and forced_token must not exceed V");
   dim3 grid(R), block(256);
 #define TOPK_LAUNCH(TT, KM) hipLaunchKernelGGL((row_lse_topk_kernel<TT, KM>), grid, block, 0, (hipStream_t)stream, V, (const TT*)logits, ld, k, forced_token, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx, (const int32_t*)nullptr)
   if (dtype == MIC_BF16) { if (k <= 8) TOPK_LAUNCH(uint16_t, 8); else if (k <= 16) TOPK_LAUNCH(uint16_t, 16); else if (k <= 32) TOPK_LAUNCH(uint16_t, 32); else TOPK_LAUNCH(uint16_t, 64); }
@@ -407,6 +409,7 @@ extern "C" int mic_row_topk_tiles(int dtype, int R, int V, const void* logits, i
   const int ntiles = (V + 63) / 64;
   MIC_CHECK(R > 0 && V > 0 && ld >= V && k >= 1 && k <= TOPK_MAX && logits && rowstat && top_val && top_idx && stat_ld >= ntiles && ntiles <= 4096,
             "mic_row_topk_tiles: bad args (V <= 262144)");
+  MIC_CHECK(k <= V, "mic_row_topk_tiles: k must not exceed V");
   dim3 grid(R), block(256);
   if (dtype == MIC_BF16)
     hipLaunchKernelGGL(row_topk_tiles_kernel<uint16_t>, grid, block, 0, (hipStream_t)stream, V, (const uint16_t*)logits, ld, (const float2*)rowstat, stat_ld, ntiles, k, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx);
@@ -675,7 +678,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(int R, int V, const T
 extern "C" int mic_sample_rows(int dtype, int R, int V, const void* logits, int ld, uint32_t key0, uint32_t key1,
                                float temperature, int forced_token, int suppress_eos, int eos_token_id,
                                const float* min_keep, const int32_t* tie_limit, int32_t* out_idx, void* stream) {
-  MIC_CHECK(R > 0 && V > 0 && logits && out_idx && temperature > 0.f, "mic_sample_rows: bad args");
+  MIC_CHECK(R > 0 && V > 0 && ld >= V && logits && out_idx && temperature > 0.f && forced_token < V, "mic_sample_rows: bad args");
   MIC_CHECK((uint64_t)R * (uint64_t)V < (1ull << 32), "mic_sample_rows: R*V must fit the 32-bit threefry counter");
   if (forced_token >= 0) {  // ForcedBOS / ForcedEOS leave one finite logit: the categorical draw is that token
     hipLaunchKernelGGL(fill_i32_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, out_idx, R, forced_token);
@@ -699,8 +702,8 @@ extern "C" int mic_sample_rows(int dtype, int R, int V, const void* logits, int 
 // few (by index) of the entries equal to it" — found per row by a 3-pass radix descent over order-preserving 32-bit keys
 // (11 + 11 + 10 bits; LDS histograms of counts for top-k, of fixed-point masses for top-p so the sums are exact and
 // order-independent).  Output per row: thr (fp32 value) and tie_limit: keep v > thr, or v == thr and index < tie_limit.
-__device__ __forceinline__ uint32_t okey(float v) {  // ascending order-preserving key
-  const uint32_t u = __float_as_uint(v);
+__device__ __forceinline__ uint32_t okey(float v) {  // ascending order-preserving key; -0 := +0, so that keys differ exactly where < does
+  const uint32_t u = __float_as_uint(v == 0.f ? 0.f : v);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float okey_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
@@ -850,7 +853,7 @@ __global__ __launch_bounds__(WARP_T) void warp_threshold_kernel(int V, const T* 
 
 extern "C" int mic_warp_thresholds(int dtype, int R, int V, const void* logits, int ld, float temperature, int suppress_eos,
                                    int eos_token_id, int top_k, float top_p, float* thr, int32_t* tie_limit, void* stream) {
-  MIC_CHECK(R > 0 && V > 0 && logits && thr && tie_limit && temperature > 0.f && top_p > 0.f, "mic_warp_thresholds: bad args");
+  MIC_CHECK(R > 0 && V > 0 && ld >= V && logits && thr && tie_limit && temperature > 0.f && top_p > 0.f, "mic_warp_thresholds: bad args");
   dim3 grid(R), block(WARP_T);
   if (dtype == MIC_BF16)
     hipLaunchKernelGGL(warp_threshold_kernel<uint16_t>, grid, block, 0, (hipStream_t)stream, V, (const uint16_t*)logits, ld, temperature, suppress_eos, eos_token_id, top_k, top_p, thr, tie_limit);
