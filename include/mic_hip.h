@@ -488,6 +488,25 @@ int mic_adamw_acc(int64_t n, float* p, float* m, float* v, const float* g, const
 int mic_adamw_rows_acc(int64_t rows, int width, const uint8_t* row_flag, int want, float* p, float* m, float* v, const float* g,
                        const float* acc, void* p_lp, const float* hyper, double b1, double b2, double eps, double wd, float grad_scale,
                        void* stream);
+/* Global-norm gradient clipping: optax.chain(clip_by_global_norm(c), adamw(...)).  The reference builds optax.adamw alone
+ * (main.py:629-635) and never reads training_args.max_grad_norm, so this is opt-in; it sits between `lax.pmean(grad)` and
+ * `state.apply_gradients` (main.py:698-701), on the gradient AdamW consumes: x = g, or fp32(g + acc) on the last micro-step of an
+ * accumulation, times grad_scale.
+ * mic_grad_sumsq: partials[b] = the sum of x^2 over the elements block b walks, b < mic_grad_sumsq_slots(n) — exactly that many
+ *   floats are plain-stored (no atomics, nothing has to be zeroed), in a fixed summation order: the same bytes give the same bits.
+ *   Squares and sums in fp32 (|x| > ~1.8e19 overflows to inf, as an fp32 computation does).  acc may be NULL; n % 4 == 0, g and acc
+ *   16-byte aligned.  mic_grad_sumsq_slots is the single source of that launch geometry (0 for n <= 0).
+ * mic_clip_coef: one block adds `count` slots in fp64 in a fixed order; norm = grad_scale * sqrt(S), coef = grad_scale if
+ *   norm < max_norm (optax's strict trigger) else grad_scale * max_norm / norm, each rounded once to fp32: out2 = {norm, coef}.  No
+ *   special case for zero or non-finite norms (0 -> grad_scale, inf -> 0, NaN -> NaN); max_norm = inf measures without clipping.
+ * mic_adamw_clip: mic_adamw (acc == NULL) or mic_adamw_acc with grad_scale read from coef[0] on the device — bit for bit the update
+ *   of those entry points called with that float; p, m, v, g, acc 16-byte aligned, p_lp (may be NULL) 8-byte.
+ * A refused call (MIC_EINVAL) has written nothing. */
+int64_t mic_grad_sumsq_slots(int64_t n);
+int mic_grad_sumsq(int64_t n, const float* g, const float* acc, float* partials, void* stream);
+int mic_clip_coef(const float* partials, int64_t count, float grad_scale, double max_norm, float* out2, void* stream);
+int mic_adamw_clip(int64_t n, float* p, float* m, float* v, const float* g, const float* acc, void* p_lp, const float* hyper,
+                   const float* coef, double b1, double b2, double eps, double wd, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Generation epilogues

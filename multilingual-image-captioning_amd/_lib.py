@@ -144,6 +144,10 @@ _SIGS = {
     "mic_grad_accumulate": ([_i64, _p, _p, _i, _p], C.c_int),
     "mic_adamw_acc": ([_i64, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _f, _p], C.c_int),
     "mic_adamw_rows_acc": ([_i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _f, _p], C.c_int),
+    "mic_grad_sumsq_slots": ([_i64], C.c_int64),
+    "mic_grad_sumsq": ([_i64, _p, _p, _p, _p], C.c_int),
+    "mic_clip_coef": ([_p, _i64, _f, C.c_double, _p, _p], C.c_int),
+    "mic_adamw_clip": ([_i64, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _p], C.c_int),
     "mic_row_lse_topk": ([_i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p], C.c_int),
     "mic_beam_step": ([C.POINTER(BeamStepArgs), _p], C.c_int),
     "mic_row_forced_topk": ([_i, _i, _p, _p, _p, _p, _p], C.c_int),

@@ -496,6 +496,38 @@ def grad_accumulate(dst, src, init=False, n=None):
     L.check(L.lib().mic_grad_accumulate(int(n), _p(dst), _p(src), int(bool(init)), _stream()), "mic_grad_accumulate")
 
 
+def grad_sumsq_slots(n) -> int:
+    """how many floats `grad_sumsq` over n elements writes (mic_grad_sumsq_slots: the kernel's launch geometry; no device needed)"""
+    return int(L.lib().mic_grad_sumsq_slots(int(n)))
+
+
+def grad_sumsq(g, partials, acc=None, n=None):
+    """partials[0 .. grad_sumsq_slots(n)) = per-block sums of g^2 (acc: of fp32(g + acc)^2) over n fp32 elements (default: all of g),
+    fixed summation order, plain stores — mic_grad_sumsq.  Returns the number of slots written."""
+    n = int(n if n is not None else g.numel())
+    slots = grad_sumsq_slots(n)
+    if partials.dtype != torch.float32 or partials.numel() < slots:
+        raise L.MicError(f"grad_sumsq: partials must hold {slots} fp32 slots")
+    L.check(L.lib().mic_grad_sumsq(n, _p(g), _p(acc), _p(partials), _stream()), "mic_grad_sumsq")
+    return slots
+
+
+def clip_coef(partials, count, grad_scale, max_norm, out2):
+    """out2 = {norm, coef} (fp32) of optax.clip_by_global_norm(max_norm) over the first `count` slots: norm = grad_scale * sqrt(sum),
+    coef = grad_scale if norm < max_norm else grad_scale * max_norm / norm, in fp64 on the device — mic_clip_coef"""
+    if out2.dtype != torch.float32 or out2.numel() < 2 or partials.numel() < int(count):
+        raise L.MicError("clip_coef: out2 must hold 2 fp32 values and partials `count` slots")
+    L.check(L.lib().mic_clip_coef(_p(partials), int(count), float(grad_scale), float(max_norm), _p(out2), _stream()), "mic_clip_coef")
+    return out2
+
+
+def adamw_clip(p, m, v, g, p_lp, hyper, coef, b1, b2, eps, wd, n=None, acc=None):
+    """`adamw` with grad_scale read from the device scalar coef[0] (mic_adamw_clip): no host round trip for the clipping coefficient"""
+    n = n if n is not None else p.numel()
+    L.check(L.lib().mic_adamw_clip(int(n), _p(p), _p(m), _p(v), _p(g), _p(acc), _p(p_lp), _p(hyper), _p(coef), float(b1), float(b2), float(eps),
+                                   float(wd), _stream()), "mic_adamw_clip")
+
+
 def row_flags(ids, n_ids, flags):
     """flags[:] = 0; flags[ids[i]] = 1 for i < n_ids (uint8 flags, int32 ids)"""
     L.check(L.lib().mic_row_flags(_p(ids), int(n_ids), _p(flags), flags.numel(), _stream()), "mic_row_flags")

@@ -496,13 +496,24 @@ class Trainer:
     backward (`acc += g`, 12 B/element), and on the N-th call AdamW reads `g + acc` itself.  With several ranks nothing is exchanged on
     the first N - 1 calls; on the N-th, `g += acc` runs in front of every bucket's all-reduce.  A call that is not the N-th returns its
     micro-batch's loss and the pending step's learning rate; the N-th returns the mean loss of the N micro-batches.  A reference
-    run at 8 devices x 64 images is `accumulate_steps=8` at a per-device batch of 64 on one GPU."""
+    run at 8 devices x 64 images is `accumulate_steps=8` at a per-device batch of 64 on one GPU.
+
+    Gradient clipping (`max_grad_norm=c`): `optax.chain(clip_by_global_norm(c), adamw(...))`.  The reference builds `optax.adamw` alone
+    (main.py:629-635) and never reads `training_args.max_grad_norm`, so this is opt-in and the default step stays what it is.  The
+    clipped quantity is the gradient AdamW consumes — the mean over ranks and micro-steps, `gscale * x` with x the summed gradient
+    (`g`, or `fp32(g + acc)` on the last micro-step of an accumulation on one rank): norm = gscale * sqrt(sum x^2), and AdamW runs with
+    grad_scale = gscale if norm < c (optax's strict trigger), gscale * c / norm otherwise; no special case for zero or non-finite
+    norms.  The sum of squares runs per gradient bucket on the optimizer stream beside backward, in a fixed summation order (squares
+    in fp32, partials added in fp64); AdamW can no longer start before the last gradient exists, so it leaves the buckets: one pass
+    over the whole buffer behind backward that reads the coefficient from device memory — the host never waits for the norm.  Every
+    `train_step` call that takes the optimizer step additionally returns "grad_norm", the pre-clip norm as a fresh device scalar
+    (identical on all ranks by construction); `c = math.inf` measures without clipping."""
 
     def __init__(self, model, learning_rate_fn: Callable[[int], float], b1=0.9, b2=0.999, eps=1e-8, weight_decay=0.0,
                  label_smoothing_factor=0.0, seed: int = 42, bucket_mb: float = 64.0, group=None, compact_head: bool = True,
                  overlap_optimizer: bool = True, grad_comm_dtype=None, gemm_dtype: Optional[str] = None,
                  fp8_scaling: str = "delayed", pack_rows: bool = True, comm_cus: Optional[int] = None, emulate_comm: int = 0,
-                 fp8_head: Optional[str] = None, accumulate_steps: int = 1):
+                 fp8_head: Optional[str] = None, accumulate_steps: int = 1, max_grad_norm: Optional[float] = None):
         """pack_rows (bfloat16 mode, with compact_head): the decoder runs on the valid caption positions only (`packed_rows`);
         exact — padded positions neither carry loss nor are attended to — and ~1/3 fewer decoder rows on ragged captions.  Needs
         prefix-shaped masks available on the host: a numpy / CPU `attention_mask`, or `batch["packed_rows"]` from the collate
@@ -518,11 +529,28 @@ class Trainer:
         emulate_comm = N (one GPU only; bench.py --emulate-comm): every bucket's exchange is replaced by a kernel holding
         `comm_cus` CUs for the projected duration of its all-reduce among N ranks — a scheduling probe, not a scaling result.
         accumulate_steps = N: micro-batches per optimizer step (class docstring).  Not combined with gemm_dtype="fp8" (the delayed
-        scales and the weight re-quantisation inside the optimizer passes assume one pass per step) or with emulate_comm."""
+        scales and the weight re-quantisation inside the optimizer passes assume one pass per step) or with emulate_comm.
+        max_grad_norm = c (a real number > 0, math.inf allowed; default None = off, the reference's step): global-norm clipping
+        in front of AdamW (class docstring).  c = inf measures the norm without clipping.  Not combined with gemm_dtype="fp8" (the
+        two-phase refresh of the fp8 weight copies keys on per-bucket optimizer progress) or with emulate_comm."""
+        import math
+        import numbers
+
         import torch.distributed as dist
 
         if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer)) or accumulate_steps < 1:
             raise ValueError(f"accumulate_steps must be an integer >= 1, got {accumulate_steps!r}")
+        if max_grad_norm is not None:
+            if (isinstance(max_grad_norm, (bool, np.bool_)) or not isinstance(max_grad_norm, numbers.Real) or math.isnan(max_grad_norm)
+                    or not max_grad_norm > 0):
+                raise ValueError(f"max_grad_norm must be None or a real number > 0 (math.inf allowed), got {max_grad_norm!r}")
+            if emulate_comm:
+                raise ValueError("max_grad_norm is not supported together with emulate_comm (out of scope: the stand-in exchange models "
+                                 "the step whose optimizer runs per bucket)")
+            if gemm_dtype == "fp8" or getattr(model.engine, "fp8", False):
+                raise ValueError("max_grad_norm is not supported together with gemm_dtype='fp8' (out of scope: the two-phase refresh of the "
+                                 "fp8 weight copies keys on per-bucket optimizer progress)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         # (tools/accumulate_probe.py switches a live Trainer between N and 1 by writing `accumulate_steps` and `_gscale`: state derived
         # from N in this constructor beyond those two — and buffers that only need to exist — has to be added to its `mode()` too)
         self.accumulate_steps = int(accumulate_steps)
@@ -597,11 +625,15 @@ class Trainer:
         # early on every row this step's decoder ids do not touch and late on the <= world*B*T rows they do (`_adamw_slice` /
         # `_adamw_shared_late`; MIC_OPT_SPLIT_SHARED=0: the whole segment waits for the end).  MIC_OPT_CUS: CUs of the optimizer
         # stream's mask.
-        self._split_shared = (self.overlap_optimizer and model.device.type == "cuda"
+        # Clipping (max_grad_norm): AdamW cannot start before the last gradient exists, so the optimizer leaves the buckets — the row
+        # split only serves the early passes and is off; what runs per bucket beside backward is the bucket's sum of squares.
+        clip = self.max_grad_norm is not None
+        self._split_shared = (self.overlap_optimizer and model.device.type == "cuda" and not clip
                               and _os.environ.get("MIC_OPT_SPLIT_SHARED", "1") != "0" and sh.numel % st.d == 0)
         self._sh = (sh.offset, sh.offset + sh.numel, st.d)
         self._row_flag = torch.zeros(sh.numel // st.d, dtype=torch.uint8, device=model.device) if self._split_shared else None
-        opt_cus = int(_os.environ.get("MIC_OPT_CUS", str(OPT_CUS_DEFAULT))) if (model.device.type == "cuda" and self._split_shared) else 0
+        opt_cus = (int(_os.environ.get("MIC_OPT_CUS", str(OPT_CUS_DEFAULT)))
+                   if (model.device.type == "cuda" and (self._split_shared or (clip and self.overlap_optimizer))) else 0)
         import weakref
 
         me = weakref.ref(self)  # the reducer's callbacks must not own the Trainer (Trainer -> reducer -> bound method -> Trainer is a cycle
@@ -610,7 +642,10 @@ class Trainer:
         # half of the gradient, still reads the weights) when the row split is on, "end" otherwise
         gate = "next" if self._split_shared else "end"
         when = [gate if (b < sh.offset + sh.numel and e > sh.offset) else "exchanged" for (b, e) in self.buckets]
-        self.reducer = GradReducer(st.grad, self.buckets, group, on_ready=(lambda b, e: me()._adamw_slice(b, e)) if self.overlap_optimizer else None,
+        # (clipping: `gate` is "end" — the pieces of the tied embedding receive the sparse input-embedding rows late, with several ranks
+        # only inside finish(before=_scatter_embedding_rows) — and every other bucket's sum of squares runs right behind its exchange)
+        on_ready = (lambda b, e: me()._sumsq_slice(b, e)) if clip else (lambda b, e: me()._adamw_slice(b, e))
+        self.reducer = GradReducer(st.grad, self.buckets, group, on_ready=on_ready if self.overlap_optimizer else None,
                                    ready_when=when, comm_dtype=self.grad_comm_dtype, opt_cus=opt_cus,
                                    emulate=dict(world=emu_world, cus=self.comm_cus or COMM_CUS_DEFAULT, comm_bytes=cb) if emu_world > 1 else None)
         self.metrics_buf = torch.zeros(2, dtype=torch.float32, device=model.device)
@@ -631,6 +666,38 @@ class Trainer:
             self._when_acc = ["end" if (b < sh.offset + sh.numel and e > sh.offset) else "exchanged" for (b, e) in self.buckets]
             self._acc_cb = lambda b, e: me()._accumulate_slice(b, e)
             self._pre_cb = lambda b, e: me()._add_acc_slice(b, e)
+        # clipping: one slot range per bucket in a partials buffer (laid out once, from the kernel's own launch geometry), or the slots
+        # of ONE pass over the whole buffer when nothing runs per bucket; (norm, coef) of the step.  None without max_grad_norm.
+        # (tools/clip_probe.py switches a live Trainer between the clipped and the plain step by writing `_clip_out`, `_split_shared`,
+        # `_row_flag` and the reducer's `on_ready` / `ready_when`: state derived from max_grad_norm beyond those has to be added to its
+        # `mode()` too)
+        self._clip_partials = self._clip_out = None
+        if clip:
+            self._clip_off, n_slots = {}, 0
+            for (b, e) in (self.buckets if self.reducer.on_ready is not None else [(0, st.numel)]):
+                self._clip_off[b] = n_slots
+                n_slots += ops.grad_sumsq_slots(e - b)
+            self._clip_slots = n_slots
+            self._clip_partials = torch.empty(n_slots, dtype=torch.float32, device=model.device)
+            self._clip_out = torch.empty(2, dtype=torch.float32, device=model.device)
+
+    def _sumsq_slice(self, b: int, e: int):
+        """clipping: the sum of squares of flat slice [b, e) of the gradient AdamW will consume (g, or g + acc on the last micro-step of
+        an accumulation on one rank) into the slice's own range of the partials buffer — on the reducer's side stream, beside backward"""
+        st = self.model.store
+        off = self._clip_off[b]
+        ops.grad_sumsq(st.grad[b:e], self._clip_partials[off:], acc=st.acc[b:e] if self._use_acc else None, n=e - b)
+
+    def _clipped_adamw(self, per_bucket: bool):
+        """clipping, behind finish() on the step's own stream: (norm, coef) from all slots, then ONE AdamW over the whole buffer that
+        reads coef from the device"""
+        st = self.model.store
+        acc = st.acc if self._use_acc else None
+        if not per_bucket:
+            ops.grad_sumsq(st.grad, self._clip_partials, acc=acc)
+        ops.clip_coef(self._clip_partials, self._clip_slots, self._gscale, self.max_grad_norm, self._clip_out)
+        ops.adamw_clip(st.master, st.m, st.v, st.grad, None if st.lp is st.master else st.lp, self.hyper, self._clip_out[1:2], self.b1,
+                       self.b2, self.eps, self.wd, acc=acc)
 
     def _adamw_slice(self, b: int, e: int):
         """AdamW on flat slice [b, e) — runs on the reducer's side stream right after that bucket's all-reduce.  The part of the
@@ -866,7 +933,9 @@ class Trainer:
             # sparse embedding-row exchange, the optimizer passes that had to wait for it, and the flagged rows of the tied embedding
             r.finish(before=self._scatter_embedding_rows if self.world > 1 else None,
                      after=self._adamw_shared_late if (self._split_shared and not self._late_done) else None)
-            if not self.overlap_optimizer:
+            if self._clip_out is not None:
+                self._clipped_adamw(per_bucket)
+            elif not self.overlap_optimizer:
                 ops.adamw(st.master, st.m, st.v, st.grad, None if st.lp is st.master else st.lp, self.hyper, self.b1, self.b2, self.eps,
                           self.wd, grad_scale=self._gscale, acc=st.acc if self._use_acc else None)
             m.invalidate_params_cache(by_optimizer=True)
@@ -892,11 +961,18 @@ class Trainer:
         self._loss_sum = None
         if self.world == 1:
             # one launch instead of three (two copies + a clone) in the gap between two steps; fresh storage per step (callers keep these)
+            if self._clip_out is not None:
+                out = torch.cat((mean, self.hyper[0:1], self._clip_out[0:1]))
+                return {"loss": out[0], "learning_rate": out[1], "grad_norm": out[2]}
             out = torch.cat((mean, self.hyper[0:1]))
             return {"loss": out[0], "learning_rate": out[1]}
         self.metrics_buf[0:1].copy_(mean)
         self.metrics_buf[1:2].copy_(self.hyper[0:1])  # lr, device to device (a Python scalar assigned into a device tensor syncs)
-        return self._pmean_metrics()
+        out = self._pmean_metrics()
+        if self._clip_out is not None:
+            # the pre-clip norm: every rank summed the same all-reduced bytes in the same order, so it needs no pmean
+            out["grad_norm"] = self._clip_out[0].clone()
+        return out
 
     def eval_step(self, batch: Dict) -> Dict[str, float]:
         """main.py:710-721 (train=False, no dropout)."""

@@ -20,7 +20,8 @@ TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
 # units whose listings the Makefile writes to build/new/ (NEW_SRCS), each with a table of its own beside TABLE: {unit: table}.  This
 # tool shows, compares and --updates them with the rest, so that no kernel of the library is missing from its output.
 NEW_BUILD = os.path.join(BUILD, "new")
-NEW_TABLES = {"accumulate": os.path.join(ROOT, "tests", "golden", "kernel_resources_accumulate.json")}
+NEW_TABLES = {"accumulate": os.path.join(ROOT, "tests", "golden", "kernel_resources_accumulate.json"),
+              "clip": os.path.join(ROOT, "tests", "golden", "kernel_resources_clip.json")}
 FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
           "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
 
