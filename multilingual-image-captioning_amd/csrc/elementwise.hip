@@ -1,5 +1,5 @@
 // elementwise.hip — HBM-bound ops around the GEMMs: ViT im2col/assemble, decoder token embedding fwd/bwd,
-// cross-entropy rows/backward, bias column sums, casts, dropout-mask materialisation, fused AdamW.
+// cross-entropy rows/backward, bias column sums, casts, dropout-mask materialisation.
 #include "common.h"
 #include <stdarg.h>
 #include <type_traits>
@@ -1172,71 +1172,8 @@ extern "C" int mic_copy_rows(int dtype, int n, int width, const void* src, int l
   });
 }
 
-// ------------------------------------------------------------------ fused AdamW over the flat parameter buffer (K15)
-// ROWS: the buffer is [rows][width] and only the rows with (row_flag[row] != 0) == want are updated — the tied embedding's
-// AdamW in two passes (mic_adamw_rows): AdamW is elementwise, so the split is exact.
-template <bool ROWS>
-__global__ __launch_bounds__(256) void adamw_kernel(long n, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                    const float* __restrict__ g, uint16_t* __restrict__ p_lp,
-                                                    const float* __restrict__ hyper, float b1, float b2, float omb1, float omb2,
-                                                    float eps, float wd, float gscale, const uint8_t* __restrict__ row_flag,
-                                                    int row_f4, int want) {
-  const float lr = hyper[0], t = hyper[1];
-  const float bc1 = 1.0f - powf(b1, t), bc2 = 1.0f - powf(b2, t);
-  const long n4 = n >> 2;
-  // ROWS: a block walks whole rows (one flag test per row and block, uniform), its threads the row's float4s
-  const long outer_n = ROWS ? n4 / row_f4 : n4;
-  const long outer_0 = ROWS ? blockIdx.x : (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long outer_step = ROWS ? gridDim.x : (long)gridDim.x * blockDim.x;
-  for (long o = outer_0; o < outer_n; o += outer_step) {
-    if constexpr (ROWS) {
-      if ((row_flag[o] != 0) != (want != 0)) continue;
-    }
-    for (long e = ROWS ? o * row_f4 + threadIdx.x : o; e < (ROWS ? (o + 1) * row_f4 : o + 1); e += ROWS ? blockDim.x : 1) {
-    float4 pp = reinterpret_cast<float4*>(p)[e], mm = reinterpret_cast<float4*>(m)[e], vv = reinterpret_cast<float4*>(v)[e];
-    const float4 gg = reinterpret_cast<const float4*>(g)[e];
-    float pa[4] = {pp.x, pp.y, pp.z, pp.w}, ma[4] = {mm.x, mm.y, mm.z, mm.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
-    const float ga[4] = {gg.x * gscale, gg.y * gscale, gg.z * gscale, gg.w * gscale};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      ma[i] = b1 * ma[i] + omb1 * ga[i];
-      va[i] = b2 * va[i] + omb2 * ga[i] * ga[i];
-      const float upd = (ma[i] / bc1) / (sqrtf(va[i] / bc2) + eps) + wd * pa[i];
-      pa[i] -= lr * upd;
-    }
-    reinterpret_cast<float4*>(p)[e] = make_float4(pa[0], pa[1], pa[2], pa[3]);
-    reinterpret_cast<float4*>(m)[e] = make_float4(ma[0], ma[1], ma[2], ma[3]);
-    reinterpret_cast<float4*>(v)[e] = make_float4(va[0], va[1], va[2], va[3]);
-    if (p_lp) {
-      uint2 q;
-      q.x = f2bf_pk(pa[0], pa[1]);
-      q.y = f2bf_pk(pa[2], pa[3]);
-      reinterpret_cast<uint2*>(p_lp)[e] = q;
-    }
-    }
-  }
-}
-extern "C" int mic_adamw(int64_t n, float* p, float* m, float* v, const float* g, void* p_lp, const float* hyper, double b1,
-                         double b2, double eps, double wd, float grad_scale, void* stream) {
-  MIC_CHECK(n > 0 && n % 4 == 0 && p && m && v && g && hyper, "mic_adamw: bad args (n must be a multiple of 4)");
-  long nb = (n / 4 + 255) / 256; if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(adamw_kernel<false>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, (long)n, p, m, v, g, (uint16_t*)p_lp, hyper, (float)b1, (float)b2,
-                     (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)wd, grad_scale, (const uint8_t*)nullptr, 1, 0);
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
-}
-
-extern "C" int mic_adamw_rows(int64_t rows, int width, const uint8_t* row_flag, int want, float* p, float* m, float* v, const float* g,
-                              void* p_lp, const float* hyper, double b1, double b2, double eps, double wd, float grad_scale, void* stream) {
-  MIC_CHECK(rows > 0 && width > 0 && width % 4 == 0 && row_flag && p && m && v && g && hyper, "mic_adamw_rows: bad args (width must be a multiple of 4)");
-  const long n = (long)rows * width;
-  long nb = (n / 4 + 255) / 256; if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(adamw_kernel<true>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, n, p, m, v, g, (uint16_t*)p_lp, hyper, (float)b1, (float)b2,
-                     (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)wd, grad_scale, row_flag, width / 4, want);
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
-}
-
+// ------------------------------------------------------------------ row flags of mic_adamw_rows (optimizer.hip)
+// flags[n_rows] zero-filled, then flags[ids[i]] = 1; ids outside [0, n_rows) are ignored
 __global__ __launch_bounds__(256) void row_flags_kernel(const int32_t* __restrict__ ids, int n_ids, uint8_t* __restrict__ flags, int n_rows) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n_ids) {

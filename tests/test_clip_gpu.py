@@ -1,5 +1,5 @@
 """Global-norm gradient clipping: `Trainer(max_grad_norm=c)` = optax.chain(clip_by_global_norm(c), adamw(...)) on the gradient AdamW
-consumes, and the kernels of csrc/clip.hip it is made of.
+consumes, and the kernels of csrc/optimizer.hip it is made of.
 
 The first Adam step is lr * g / (|g| + eps) and Adam is invariant under a common scale of the gradient, so the weights alone cannot
 show that clipping happened: the decisive observables are the returned norm and the moments m, v (tests/util_clip.py::assert_tight),

@@ -1,5 +1,5 @@
-"""Row-op conformance on the MI355X: the LayerNorm family (csrc/norm.hip), the materialised-logits cross-entropy family and AdamW
-(csrc/elementwise.hip) on every case of tests/util_rowop_cases.py, in bf16 and fp32 where the entry point takes a dtype, against
+"""Row-op conformance on the MI355X: the LayerNorm family (csrc/norm.hip), the materialised-logits cross-entropy family
+(csrc/elementwise.hip) and AdamW (csrc/optimizer.hip) on every case of tests/util_rowop_cases.py, in bf16 and fp32 where the entry point takes a dtype, against
 the fp64 references and derived per-element bounds of tests/util_rowop_ref.py.  Around every call:
   - outputs are windows in canary-filled allocations (extra rows, a row stride wider than the columns where the entry point takes
     one, a base offset that keeps the documented alignment); every element outside the window keeps its bits;

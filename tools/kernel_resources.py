@@ -3,7 +3,6 @@ Makefile leaves in csrc/build/<unit>.res): VGPRs / AGPRs / SGPRs, scratch, spill
 
   python tools/kernel_resources.py            table of the current build beside the committed one, differences marked
   python tools/kernel_resources.py --update   rewrite tests/golden/kernel_resources.json from the current build
-                                              (and the tables of the units listed in NEW_TABLES)
 
 The guard (tests/test_kernel_resources_cpu.py) fails on scratch or spills in any kernel, on an occupancy below the committed one, and
 on kernels the table does not know — the two silent regressions of round 4 (272 B of scratch in the non-PLAIN 256x256 epilogues, a
@@ -17,11 +16,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "multilingual-image-captioning_amd", "csrc", "build")
 TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
-# units whose listings the Makefile writes to build/new/ (NEW_SRCS), each with a table of its own beside TABLE: {unit: table}.  This
-# tool shows, compares and --updates them with the rest, so that no kernel of the library is missing from its output.
-NEW_BUILD = os.path.join(BUILD, "new")
-NEW_TABLES = {"accumulate": os.path.join(ROOT, "tests", "golden", "kernel_resources_accumulate.json"),
-              "clip": os.path.join(ROOT, "tests", "golden", "kernel_resources_clip.json")}
 FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
           "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
 
@@ -72,18 +66,6 @@ def current():
     return units
 
 
-def current_new():
-    """{unit: {kernel: fields}} of build/new/ (the units of NEW_TABLES)"""
-    units = {}
-    for unit in NEW_TABLES:
-        f = os.path.join(NEW_BUILD, unit + ".res")
-        if os.path.exists(f):
-            k = parse_res(f)
-            dm = demangle(list(k))
-            units[unit] = {short(dm[n]): v for n, v in k.items()}
-    return units
-
-
 def compare(cur, ref):
     """list of (severity, message); severity "fail" = what the guard refuses"""
     msgs = []
@@ -118,16 +100,8 @@ def main():
         os.makedirs(os.path.dirname(TABLE), exist_ok=True)
         json.dump(cur, open(TABLE, "w"), indent=0, sort_keys=True)
         print(f"wrote {TABLE}: {sum(len(v) for v in cur.values())} kernels in {len(cur)} units")
-        for unit, ks in current_new().items():
-            json.dump({unit: ks}, open(NEW_TABLES[unit], "w"), indent=0, sort_keys=True)
-            print(f"wrote {NEW_TABLES[unit]}: {len(ks)} kernels")
         return
     ref = json.load(open(TABLE)) if os.path.exists(TABLE) else {}
-    cur = dict(cur)
-    for unit, ks in current_new().items():  # shown and compared with the rest, each against its own table
-        cur[unit] = ks
-        if os.path.exists(NEW_TABLES[unit]):
-            ref = dict(ref, **json.load(open(NEW_TABLES[unit])))
     print(f"{'unit':<12} {'kernel':<88} {'vgpr':>4} {'agpr':>4} {'sgpr':>4} {'scr':>4} {'occ':>3} {'lds':>6}")
     for unit, ks in cur.items():
         for name, v in sorted(ks.items()):
