@@ -294,6 +294,19 @@ int mic_attn_bwd_packed(int dtype, int B, int H, int Tq_max, int Tk, const int32
                         const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
                         const void* dout, int lddo, const float* lse, int causal, void* dq, int lddq, void* dk, int lddk,
                         void* dv, int lddv, void* stream);
+/* Packed rows of any length: the same contract without the one-tile limit — any Tq_max >= 1 and Tk >= 1, always on the tiled
+ * kernels (online softmax over 64-key blocks; ceil(Tq_max / 64) workgroups per (sequence, head), those behind q_len[b] leave at
+ * once).  kv_packed = 1 needs Tk == Tq_max.  lse [B][H][Tq_max], lse[(b*H + h)*Tq_max + i]: the layout of the one-tile calls.
+ * Nothing behind q_len[b] is written: no lse slot i >= q_len[b], no row of out / dq (or, kv_packed, dk / dv) outside
+ * [q_off[b], q_off[b] + q_len[b]), no column outside the head's 64.  Refused, writing nothing: NULL q_off / q_len, row strides
+ * that break 16-B alignment, kv_packed with Tk != Tq_max, a dtype other than MIC_BF16 / MIC_F32. */
+int mic_attn_fwd_packed_tiled(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
+                              const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, int causal,
+                              float* lse, void* stream);
+int mic_attn_bwd_packed_tiled(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
+                              const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
+                              const void* dout, int lddo, const float* lse, int causal, void* dq, int lddq, void* dk, int lddk,
+                              void* dv, int lddv, void* stream);
 /* mic_attn_bwd / mic_attn_bwd_packed (q_off == NULL: dense rows) of the bf16 single-tile kernel with dQ / dK / dV written as fp8
  * bytes under delayed scaling (mic_fp8_out): dq8 describes dQ's byte matrix and tensor, dk8 dK's; dV (dv8) shares dK's leading
  * dimension, scale and amax table — dK and dV are the two halves of ONE [rows][2d] (or, with dQ, [rows][3d]) gradient tensor. */

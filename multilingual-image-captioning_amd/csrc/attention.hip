@@ -355,6 +355,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(int H, int Tq_max, int Tk
 // Forward: one workgroup per (batch, head, 64-query block) walks the 64-key blocks with the online-softmax recurrence:
 // running row max / row sum in LDS, the four 32x32 output blocks in the waves' accumulators, rescaled by
 // alpha = exp(m_old - m_new) before each block's P V is added.  Per block the arithmetic is the single-tile kernel's.
+// Packed rows (pk.q_off != nullptr; PackedRows above): the grid still has ceil(Tq_max / 64) blocks per (sequence, head) — for the
+// backward's MODE 1 ceil(Tk_max / 64) — and a workgroup whose 64-row block starts at or behind its sequence's own length leaves before
+// it stages or writes anything; the walks over the other index stop at the sequence's own block count.  lse keeps the one-tile
+// packed layout lse[(b*H + h)*Tq_max + i], and no slot i >= q_len[b] is written.  Dense rows take the same code with
+// Tq = Tq_max, Tk = Tk_max: no workgroup leaves early and every address is the one it was.
 __device__ __forceinline__ unsigned long long load_key_mask_blk(const int32_t* key_mask, int b, int Tk, int k0, int lane) {
   if (!key_mask) return ~0ull;
   const int mv = k0 + lane < Tk ? key_mask[b * Tk + k0 + lane] : 0;
@@ -362,10 +367,10 @@ __device__ __forceinline__ unsigned long long load_key_mask_blk(const int32_t* k
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(int H, int Tq, int Tk, const T* __restrict__ q, int ldq,
+__global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(int H, int Tq_max, int Tk_max, const T* __restrict__ q, int ldq,
                                                              const T* __restrict__ k, int ldk, const T* __restrict__ v, int ldv,
                                                              T* __restrict__ out, int ldo, const int32_t* __restrict__ key_mask,
-                                                             int causal, float* __restrict__ lse_out) {
+                                                             int causal, float* __restrict__ lse_out, PackedRows pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TB = Tile<T>::BYTES;
   char* Qt = smem;
@@ -378,11 +383,19 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(int H, int Tq, int 
   float* l_run = m_run + 64;                              // [64]
   float* alpha_s = l_run + 64;                            // [64]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nqb = (Tq + 63) >> 6;
+  const int nqb = (Tq_max + 63) >> 6;
   const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb;
   const int b = bh / H, h = bh % H;
-  const int q0 = qb * 64, nq = min(64, Tq - q0);
-  Tile<T>::template stage<256>(Qt, q + ((size_t)b * Tq + q0) * ldq + h * 64, ldq, nq, tid);
+  int Tq = Tq_max, Tk = Tk_max;
+  size_t qr = (size_t)b * Tq_max, kr = (size_t)b * Tk_max;  // first q row / first k, v row of sequence b
+  if (pk.q_off) {
+    qr = pk.q_off[b]; Tq = pk.q_len[b];
+    if (pk.kv_packed) { kr = qr; Tk = Tq; }
+  }
+  const int q0 = qb * 64;
+  if (q0 >= Tq) return;  // (whole workgroup: a query block behind this sequence's rows)
+  const int nq = min(64, Tq - q0);
+  Tile<T>::template stage<256>(Qt, q + (qr + q0) * ldq + h * 64, ldq, nq, tid);
   if (tid < 64) { m_run[tid] = -INFINITY; l_run[tid] = 0.f; }
   const int ib = wave >> 1, jb = wave & 1, db = wave & 1;
   const int i = ib * 32 + (lane & 31);  // this lane's query (local) in the score phase
@@ -393,8 +406,8 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(int H, int Tq, int 
   for (int kb = 0; kb < nkb; ++kb) {
     const int k0 = kb * 64, nk = min(64, Tk - k0);
     __syncthreads();  // the previous block's P V has read Kt / Vt / Pt
-    Tile<T>::template stage<256>(Kt, k + ((size_t)b * Tk + k0) * ldk + h * 64, ldk, nk, tid);
-    Tile<T>::template stage<256>(Vt, v + ((size_t)b * Tk + k0) * ldv + h * 64, ldv, nk, tid);
+    Tile<T>::template stage<256>(Kt, k + (kr + k0) * ldk + h * 64, ldk, nk, tid);
+    Tile<T>::template stage<256>(Vt, v + (kr + k0) * ldv + h * 64, ldv, nk, tid);
     const unsigned long long km = load_key_mask_blk(key_mask, b, Tk, k0, lane);
     __syncthreads();
     f32x16 s;
@@ -442,13 +455,13 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(int H, int Tq, int 
     Tile<T>::template mma<false, true>(o, Pt, ib * 32, Vt, db * 32, lane);
   }
   __syncthreads();
-  if (tid < 64 && tid < nq && lse_out) lse_out[((size_t)b * H + h) * Tq + q0 + tid] = m_run[tid] + logf(l_run[tid]);
+  if (tid < 64 && tid < nq && lse_out) lse_out[((size_t)b * H + h) * Tq_max + q0 + tid] = m_run[tid] + logf(l_run[tid]);
   const int d = db * 32 + (lane & 31);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int qi = ib * 32 + acc_row(r, lane);
     const float lq = l_run[qi];  // 0: a row with no admissible key in any block -> output row 0, lse -inf
-    if (qi < nq) ElemT<T>::st(out + ((size_t)b * Tq + q0 + qi) * ldo + h * 64 + d, lq > 0.f ? o[r] / lq : 0.f);
+    if (qi < nq) ElemT<T>::st(out + (qr + q0 + qi) * ldo + h * 64 + d, lq > 0.f ? o[r] / lq : 0.f);
   }
 }
 
@@ -458,12 +471,12 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(int H, int Tq, int 
 //           dV = sum_i P_ij^T dO_i.
 // No atomics, deterministic; the score blocks are computed twice (the contraction over the other index is the expensive part).
 template <typename T, int MODE>
-__global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(int H, int Tq, int Tk, const T* __restrict__ q, int ldq,
+__global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(int H, int Tq_max, int Tk_max, const T* __restrict__ q, int ldq,
                                                              const T* __restrict__ k, int ldk, const T* __restrict__ v, int ldv,
                                                              const T* __restrict__ out, int ldo, const T* __restrict__ dout, int lddo,
                                                              const float* __restrict__ lse_in, const int32_t* __restrict__ key_mask,
                                                              int causal, T* __restrict__ dq, int lddq, T* __restrict__ dk, int lddk,
-                                                             T* __restrict__ dv, int lddv) {
+                                                             T* __restrict__ dv, int lddv, PackedRows pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int TB = Tile<T>::BYTES;
   char* Qt = smem;
@@ -475,20 +488,28 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(int H, int Tq, int 
   float* lse_s = reinterpret_cast<float*>(smem + 6 * TB);
   float* delta_s = lse_s + 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nqb = (Tq + 63) >> 6, nkb = (Tk + 63) >> 6;
-  const int nfix = MODE == 0 ? nqb : nkb;
+  const int nfix = ((MODE == 0 ? Tq_max : Tk_max) + 63) >> 6;
   const int fix = blockIdx.x % nfix, bh = blockIdx.x / nfix;
   const int b = bh / H, h = bh % H;
+  int Tq = Tq_max, Tk = Tk_max;
+  size_t qr = (size_t)b * Tq_max, kr = (size_t)b * Tk_max;  // first q row / first k, v row of sequence b
+  if (pk.q_off) {
+    qr = pk.q_off[b]; Tq = pk.q_len[b];
+    if (pk.kv_packed) { kr = qr; Tk = Tq; }
+  }
+  if (fix * 64 >= (MODE == 0 ? Tq : Tk)) return;  // (whole workgroup: a block behind this sequence's rows)
+  const int nqb = (Tq + 63) >> 6, nkb = (Tk + 63) >> 6;
+  const size_t lse0 = ((size_t)b * H + h) * Tq_max;
 
   auto stage_q = [&](int qb) {
     const int q0 = qb * 64, nq = min(64, Tq - q0);
-    Tile<T>::template stage<256>(Qt, q + ((size_t)b * Tq + q0) * ldq + h * 64, ldq, nq, tid);
-    Tile<T>::template stage<256>(dOt, dout + ((size_t)b * Tq + q0) * lddo + h * 64, lddo, nq, tid);
+    Tile<T>::template stage<256>(Qt, q + (qr + q0) * ldq + h * 64, ldq, nq, tid);
+    Tile<T>::template stage<256>(dOt, dout + (qr + q0) * lddo + h * 64, lddo, nq, tid);
     const int row = tid >> 2, part = tid & 3;  // delta_i = dO_i . O_i : thread t covers 16 of the 64 dims of row t>>2
     float dl = 0.f;
     if (row < nq) {
-      const T* orow = out + ((size_t)b * Tq + q0 + row) * ldo + h * 64 + part * 16;
-      const T* drow = dout + ((size_t)b * Tq + q0 + row) * lddo + h * 64 + part * 16;
+      const T* orow = out + (qr + q0 + row) * ldo + h * 64 + part * 16;
+      const T* drow = dout + (qr + q0 + row) * lddo + h * 64 + part * 16;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         float a[8], g[8];
@@ -501,12 +522,12 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(int H, int Tq, int 
     dl += __shfl_xor(dl, 1, 64);
     dl += __shfl_xor(dl, 2, 64);
     if (part == 0) delta_s[row] = dl;
-    if (tid < 64) lse_s[tid] = tid < nq ? lse_in[((size_t)b * H + h) * Tq + q0 + tid] : 0.f;
+    if (tid < 64) lse_s[tid] = tid < nq ? lse_in[lse0 + q0 + tid] : 0.f;
   };
   auto stage_k = [&](int kb) {
     const int k0 = kb * 64, nk = min(64, Tk - k0);
-    Tile<T>::template stage<256>(Kt, k + ((size_t)b * Tk + k0) * ldk + h * 64, ldk, nk, tid);
-    Tile<T>::template stage<256>(Vt, v + ((size_t)b * Tk + k0) * ldv + h * 64, ldv, nk, tid);
+    Tile<T>::template stage<256>(Kt, k + (kr + k0) * ldk + h * 64, ldk, nk, tid);
+    Tile<T>::template stage<256>(Vt, v + (kr + k0) * ldv + h * 64, ldv, nk, tid);
   };
   // P and dS blocks of the (qb, kb) pair into LDS (rows = queries); inadmissible pairs are exact zeros
   auto scores = [&](int qb, int kb, unsigned long long km) {
@@ -554,7 +575,7 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(int H, int Tq, int 
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int i = xb * 32 + acc_row(r, lane);
-      if (i < nq) ElemT<T>::st(dq + ((size_t)b * Tq + q0 + i) * lddq + h * 64 + d, a[r]);
+      if (i < nq) ElemT<T>::st(dq + (qr + q0 + i) * lddq + h * 64 + d, a[r]);
     }
   } else {
     const int kb = fix, k0 = kb * 64, nk = min(64, Tk - k0);
@@ -575,8 +596,8 @@ __global__ __launch_bounds__(256) void attn_bwd_tiled_kernel(int H, int Tq, int 
     for (int r = 0; r < 16; ++r) {
       const int j = xb * 32 + acc_row(r, lane);
       if (j < nk) {
-        ElemT<T>::st(dk + ((size_t)b * Tk + k0 + j) * lddk + h * 64 + d, a[r]);
-        ElemT<T>::st(dv + ((size_t)b * Tk + k0 + j) * lddv + h * 64 + d, c[r]);
+        ElemT<T>::st(dk + (kr + k0 + j) * lddk + h * 64 + d, a[r]);
+        ElemT<T>::st(dv + (kr + k0 + j) * lddv + h * 64 + d, c[r]);
       }
     }
   }
@@ -664,11 +685,11 @@ extern "C" int mic_attn_fwd(int dtype, int B, int H, int Tq, int Tk, const void*
   if (Tq > 64 || Tk > 64) {  // online-softmax walk over 64-key blocks
     dim3 grid(B * H * ((Tq + 63) / 64)), block(256);
     if (dtype == MIC_BF16) {
-      hipLaunchKernelGGL(attn_fwd_tiled_kernel<uint16_t>, grid, block, 4 * Tile<uint16_t>::BYTES + 2048, (hipStream_t)stream, H, Tq, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)out, ldo, key_mask, causal, lse);
+      hipLaunchKernelGGL(attn_fwd_tiled_kernel<uint16_t>, grid, block, 4 * Tile<uint16_t>::BYTES + 2048, (hipStream_t)stream, H, Tq, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)out, ldo, key_mask, causal, lse, PackedRows{nullptr, nullptr, 0});
     } else if (dtype == MIC_F32) {
       const size_t lds = 4 * Tile<float>::BYTES + 2048;
       if (int rc = set_lds(attn_fwd_tiled_kernel<float>, lds)) return rc;
-      hipLaunchKernelGGL(attn_fwd_tiled_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (float*)out, ldo, key_mask, causal, lse);
+      hipLaunchKernelGGL(attn_fwd_tiled_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (float*)out, ldo, key_mask, causal, lse, PackedRows{nullptr, nullptr, 0});
     } else MIC_CHECK(false, "mic_attn_fwd: bad dtype");
     MIC_LAUNCH_CHECK();
     return MIC_OK;
@@ -685,6 +706,21 @@ extern "C" int mic_attn_fwd(int dtype, int B, int H, int Tq, int Tk, const void*
   return MIC_OK;
 }
 
+// the two launches of the tiled backward: dQ over the query blocks, then dK / dV over the key blocks
+template <typename TT>
+static int launch_bwd_tiled(int B, int H, int Tq, int Tk, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out,
+                            int ldo, const void* dout, int lddo, const float* lse, const int32_t* key_mask, int causal, void* dq, int lddq,
+                            void* dk, int lddk, void* dv, int lddv, PackedRows pk, void* stream) {
+  dim3 gq(B * H * ((Tq + 63) / 64)), gk(B * H * ((Tk + 63) / 64)), block(256);
+  const size_t lds = 6 * Tile<TT>::BYTES + 512;
+  if (int rc = set_lds(attn_bwd_tiled_kernel<TT, 0>, lds)) return rc;
+  if (int rc = set_lds(attn_bwd_tiled_kernel<TT, 1>, lds)) return rc;
+  hipLaunchKernelGGL((attn_bwd_tiled_kernel<TT, 0>), gq, block, lds, (hipStream_t)stream, H, Tq, Tk, (const TT*)q, ldq, (const TT*)k, ldk, (const TT*)v, ldv, (const TT*)out, ldo, (const TT*)dout, lddo, lse, key_mask, causal, (TT*)dq, lddq, (TT*)dk, lddk, (TT*)dv, lddv, pk);
+  hipLaunchKernelGGL((attn_bwd_tiled_kernel<TT, 1>), gk, block, lds, (hipStream_t)stream, H, Tq, Tk, (const TT*)q, ldq, (const TT*)k, ldk, (const TT*)v, ldv, (const TT*)out, ldo, (const TT*)dout, lddo, lse, key_mask, causal, (TT*)dq, lddq, (TT*)dk, lddk, (TT*)dv, lddv, pk);
+  MIC_LAUNCH_CHECK();
+  return MIC_OK;
+}
+
 extern "C" int mic_attn_bwd(int dtype, int B, int H, int Tq, int Tk, const void* q, int ldq, const void* k, int ldk,
                             const void* v, int ldv, const void* out, int ldo, const void* dout, int lddo, const float* lse,
                             const int32_t* key_mask, int causal, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv,
@@ -694,21 +730,10 @@ extern "C" int mic_attn_bwd(int dtype, int B, int H, int Tq, int Tk, const void*
   const int align = dtype == MIC_BF16 ? 8 : 4;
   MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0 && ldo % align == 0 && lddo % align == 0, "mic_attn_bwd: row strides must keep 16-B alignment");
   if (Tq > 64 || Tk > 64) {
-    dim3 gq(B * H * ((Tq + 63) / 64)), gk(B * H * ((Tk + 63) / 64)), block(256);
-#define BWD_TILED(TT)                                                                                                              \
-    do {                                                                                                                           \
-      const size_t lds = 6 * Tile<TT>::BYTES + 512;                                                                                \
-      if (int rc = set_lds(attn_bwd_tiled_kernel<TT, 0>, lds)) return rc;                                                          \
-      if (int rc = set_lds(attn_bwd_tiled_kernel<TT, 1>, lds)) return rc;                                                          \
-      hipLaunchKernelGGL((attn_bwd_tiled_kernel<TT, 0>), gq, block, lds, (hipStream_t)stream, H, Tq, Tk, (const TT*)q, ldq, (const TT*)k, ldk, (const TT*)v, ldv, (const TT*)out, ldo, (const TT*)dout, lddo, lse, key_mask, causal, (TT*)dq, lddq, (TT*)dk, lddk, (TT*)dv, lddv); \
-      hipLaunchKernelGGL((attn_bwd_tiled_kernel<TT, 1>), gk, block, lds, (hipStream_t)stream, H, Tq, Tk, (const TT*)q, ldq, (const TT*)k, ldk, (const TT*)v, ldv, (const TT*)out, ldo, (const TT*)dout, lddo, lse, key_mask, causal, (TT*)dq, lddq, (TT*)dk, lddk, (TT*)dv, lddv); \
-    } while (0)
-    if (dtype == MIC_BF16) BWD_TILED(uint16_t);
-    else if (dtype == MIC_F32) BWD_TILED(float);
-    else MIC_CHECK(false, "mic_attn_bwd: bad dtype");
-#undef BWD_TILED
-    MIC_LAUNCH_CHECK();
-    return MIC_OK;
+    MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_attn_bwd: bad dtype");
+    const PackedRows pk{nullptr, nullptr, 0};
+    return dtype == MIC_BF16 ? launch_bwd_tiled<uint16_t>(B, H, Tq, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, key_mask, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream)
+                             : launch_bwd_tiled<float>(B, H, Tq, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, key_mask, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream);
   }
   dim3 grid(B * H), block(256);
   if (dtype == MIC_BF16) {
@@ -763,6 +788,45 @@ extern "C" int mic_attn_bwd_packed(int dtype, int B, int H, int Tq_max, int Tk, 
   } else MIC_CHECK(false, "mic_attn_bwd_packed: bad dtype");
   MIC_LAUNCH_CHECK();
   return MIC_OK;
+}
+
+// ------------------------------------------------------------------ packed rows, any length: always the tiled kernels
+// lse[(b*H + h)*Tq_max + i] for i < q_len[b], the layout of the one-tile packed calls; nothing behind q_len[b] is written (neither
+// lse slots nor rows of out / dq / dk / dv).  kv_packed: Tk must equal Tq_max (the keys ARE the packed rows).
+extern "C" int mic_attn_fwd_packed_tiled(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
+                                         const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                                         int causal, float* lse, void* stream) {
+  MIC_CHECK(B > 0 && H > 0 && Tq_max > 0 && Tk > 0, "mic_attn_fwd_packed_tiled: bad shape B=%d H=%d Tq_max=%d Tk=%d", B, H, Tq_max, Tk);
+  MIC_CHECK(q && k && v && out && q_off && q_len, "mic_attn_fwd_packed_tiled: null pointer");
+  MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_attn_fwd_packed_tiled: bad dtype");
+  MIC_CHECK(!kv_packed || Tk == Tq_max, "mic_attn_fwd_packed_tiled: kv_packed needs Tk == Tq_max (Tq_max=%d Tk=%d)", Tq_max, Tk);
+  const int align = dtype == MIC_BF16 ? 8 : 4;
+  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0, "mic_attn_fwd_packed_tiled: row strides must keep 16-B alignment");
+  const PackedRows pk{q_off, q_len, kv_packed};
+  dim3 grid(B * H * ((Tq_max + 63) / 64)), block(256);
+  if (dtype == MIC_BF16) {
+    hipLaunchKernelGGL(attn_fwd_tiled_kernel<uint16_t>, grid, block, 4 * Tile<uint16_t>::BYTES + 2048, (hipStream_t)stream, H, Tq_max, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)out, ldo, nullptr, causal, lse, pk);
+  } else {
+    const size_t lds = 4 * Tile<float>::BYTES + 2048;
+    if (int rc = set_lds(attn_fwd_tiled_kernel<float>, lds)) return rc;
+    hipLaunchKernelGGL(attn_fwd_tiled_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq_max, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (float*)out, ldo, nullptr, causal, lse, pk);
+  }
+  MIC_LAUNCH_CHECK();
+  return MIC_OK;
+}
+extern "C" int mic_attn_bwd_packed_tiled(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
+                                         const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
+                                         const void* dout, int lddo, const float* lse, int causal, void* dq, int lddq, void* dk, int lddk,
+                                         void* dv, int lddv, void* stream) {
+  MIC_CHECK(B > 0 && H > 0 && Tq_max > 0 && Tk > 0, "mic_attn_bwd_packed_tiled: bad shape B=%d H=%d Tq_max=%d Tk=%d", B, H, Tq_max, Tk);
+  MIC_CHECK(q && k && v && out && dout && lse && dq && dk && dv && q_off && q_len, "mic_attn_bwd_packed_tiled: null pointer");
+  MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_attn_bwd_packed_tiled: bad dtype");
+  MIC_CHECK(!kv_packed || Tk == Tq_max, "mic_attn_bwd_packed_tiled: kv_packed needs Tk == Tq_max (Tq_max=%d Tk=%d)", Tq_max, Tk);
+  const int align = dtype == MIC_BF16 ? 8 : 4;
+  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0 && ldo % align == 0 && lddo % align == 0, "mic_attn_bwd_packed_tiled: row strides must keep 16-B alignment");
+  const PackedRows pk{q_off, q_len, kv_packed};
+  return dtype == MIC_BF16 ? launch_bwd_tiled<uint16_t>(B, H, Tq_max, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, nullptr, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream)
+                           : launch_bwd_tiled<float>(B, H, Tq_max, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, nullptr, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream);
 }
 
 // fused fp8 emission of dQ / dK / dV (bf16 storage, one 64x64 tile per sequence; dense rows with q_off == NULL, packed rows otherwise)

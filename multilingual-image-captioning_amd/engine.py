@@ -31,6 +31,13 @@ def _mix(seed: int, site: int) -> int:
     return x & 0xFFFFFFFF
 
 
+def packed_attn_tiled(Tq_max: int, Tk: int) -> bool:
+    """which packed attention cores one call takes: the one-tile kernels while queries and keys fit one 64x64 tile, the tiled ones
+    (`ops.attn_*_packed_tiled`) beyond.  Self-attention asks with (T, T), cross-attention with (T, S): at T <= 64 < S only the
+    cross-attention leaves the one-tile kernels."""
+    return Tq_max > 64 or Tk > 64
+
+
 class Engine(Fp8Views):
     def __init__(self, store: ParamStore):
         self.P = store
@@ -557,8 +564,9 @@ class Engine(Fp8Views):
             ctx = self.buf(tag + "ctx", Mcap, d)
             lse = self.vec(tag + "lse", B * H * T)
             if pack is not None:
-                ops.attn_fwd_packed(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, B, H, T, T, pack[0], pack[1], kv_packed=True, ldq=3 * d, ldk=3 * d,
-                                    ldv=3 * d, ldo=d, causal=True, lse=lse)
+                fwd_packed = ops.attn_fwd_packed_tiled if packed_attn_tiled(T, T) else ops.attn_fwd_packed
+                fwd_packed(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, B, H, T, T, pack[0], pack[1], kv_packed=True, ldq=3 * d, ldk=3 * d,
+                           ldv=3 * d, ldo=d, causal=True, lse=lse)
             else:
                 ops.attn_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, B, H, T, T, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, key_mask=key_mask,
                              causal=True, lse=lse)
@@ -575,8 +583,8 @@ class Engine(Fp8Views):
             cctx = self.buf(tag + "cctx", Mcap, d)
             clse = self.vec(tag + "clse", B * H * T)
             if pack is not None:
-                ops.attn_fwd_packed(q, kv, kv[:, d:], cctx, B, H, T, S, pack[0], pack[1], kv_packed=False, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d,
-                                    lse=clse)
+                fwd_packed = ops.attn_fwd_packed_tiled if packed_attn_tiled(T, S) else ops.attn_fwd_packed
+                fwd_packed(q, kv, kv[:, d:], cctx, B, H, T, S, pack[0], pack[1], kv_packed=False, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lse=clse)
             else:
                 ops.attn_fwd(q, kv, kv[:, d:], cctx, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lse=clse)
             x2 = self.buf(tag + "x2", Mcap, d)
@@ -819,8 +827,9 @@ class Engine(Fp8Views):
                 dq = self.dyb("db.dq", l, Mcap, d)
                 dkv = dkvcat[:, l * 2 * d:] if hoist else self.dyb("db.dkv", l, Mv, 2 * d)
                 if pack is not None:
-                    ops.attn_bwd_packed(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq, dkv, dkv[:, d:], B, H, T, S, pack[0], pack[1], kv_packed=False,
-                                        ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lddo=d, lddq=d, lddk=ldkv, lddv=ldkv)
+                    bwd_packed = ops.attn_bwd_packed_tiled if packed_attn_tiled(T, S) else ops.attn_bwd_packed
+                    bwd_packed(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq, dkv, dkv[:, d:], B, H, T, S, pack[0], pack[1], kv_packed=False,
+                               ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lddo=d, lddq=d, lddk=ldkv, lddv=ldkv)
                 else:
                     ops.attn_bwd(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq, dkv, dkv[:, d:], B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d,
                                  lddo=d, lddq=d, lddk=ldkv, lddv=ldkv)
@@ -843,9 +852,10 @@ class Engine(Fp8Views):
             else:
                 dqkv = self.dyb("db.dqkv", l, Mcap, 3 * d)
                 if pack is not None:
-                    ops.attn_bwd_packed(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv, dqkv[:, d:], dqkv[:, 2 * d:], B, H, T, T, pack[0],
-                                        pack[1], kv_packed=True, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, lddq=3 * d, lddk=3 * d,
-                                        lddv=3 * d, causal=True)
+                    bwd_packed = ops.attn_bwd_packed_tiled if packed_attn_tiled(T, T) else ops.attn_bwd_packed
+                    bwd_packed(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv, dqkv[:, d:], dqkv[:, 2 * d:], B, H, T, T, pack[0],
+                               pack[1], kv_packed=True, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, lddq=3 * d, lddk=3 * d,
+                               lddv=3 * d, causal=True)
                 else:
                     ops.attn_bwd(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv, dqkv[:, d:], dqkv[:, 2 * d:], B, H, T, T, ldq=3 * d,
                                  ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, lddq=3 * d, lddk=3 * d, lddv=3 * d, key_mask=key_mask, causal=True)
@@ -1071,14 +1081,14 @@ class Engine(Fp8Views):
         return self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=False, stat=stat)
 
     def _check_pack(self, pack, rows, T: int):
-        """packed rows need the bf16-storage kernels (bf16 or fp8 GEMMs), one attention tile per sequence, and the compacted head on
-        the same rows"""
+        """packed rows need the bf16-storage kernels (bf16 or fp8 GEMMs) and the compacted head on the same rows; any seq_len and any
+        number of encoder positions (`packed_attn_tiled` picks the attention cores)"""
         if pack is None:
             return None
         if rows is None or rows[1] != pack[2]:
             raise ValueError("packed decoder rows go with the compacted LM head on the same rows (rows=(idx, n) with n == pack rows)")
-        if self.dt != torch.bfloat16 or T > 64 or self.P.S > 64:
-            raise ValueError("packed decoder rows: bfloat16 storage mode, seq_len <= 64 and at most 64 encoder positions")
+        if self.dt != torch.bfloat16:
+            raise ValueError("packed decoder rows: bfloat16 storage mode")
         return pack
 
     def ones_i32(self, n: int):

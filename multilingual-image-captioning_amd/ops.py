@@ -267,6 +267,21 @@ def attn_bwd_packed(q, k, v, out, dout, lse, dq, dk, dv, B, H, Tq_max, Tk, q_off
                                         _stream()), "mic_attn_bwd_packed")
 
 
+def attn_fwd_packed_tiled(q, k, v, out, B, H, Tq_max, Tk, q_off, q_len, *, kv_packed, ldq, ldk, ldv, ldo, causal=False, lse=None):
+    """attn_fwd_packed without the one-tile limit (any Tq_max, Tk; kv_packed needs Tk == Tq_max): the tiled kernels on packed rows,
+    lse in the same [B][H][Tq_max] layout, nothing behind q_len[b] written"""
+    L.check(L.lib().mic_attn_fwd_packed_tiled(_dt(q), B, H, Tq_max, Tk, _p(q_off), _p(q_len), int(kv_packed), _p(q), ldq, _p(k), ldk, _p(v), ldv,
+                                              _p(out), ldo, int(causal), _p(lse), _stream()), "mic_attn_fwd_packed_tiled")
+    return out
+
+
+def attn_bwd_packed_tiled(q, k, v, out, dout, lse, dq, dk, dv, B, H, Tq_max, Tk, q_off, q_len, *, kv_packed, ldq, ldk, ldv, ldo, lddo,
+                          lddq, lddk, lddv, causal=False):
+    L.check(L.lib().mic_attn_bwd_packed_tiled(_dt(q), B, H, Tq_max, Tk, _p(q_off), _p(q_len), int(kv_packed), _p(q), ldq, _p(k), ldk, _p(v), ldv,
+                                              _p(out), ldo, _p(dout), lddo, _p(lse), int(causal), _p(dq), lddq, _p(dk), lddk, _p(dv), lddv,
+                                              _stream()), "mic_attn_bwd_packed_tiled")
+
+
 def attn_bwd_q8(q, k, v, out, dout, lse, dq8, dk8, dv8, B, H, Tq, Tk, *, ldq, ldk, ldv, ldo, lddo, q_off=None, q_len=None, kv_packed=False,
                 key_mask=None, causal=False):
     """attention backward (bf16, one 64x64 tile per sequence; dense rows, or packed rows with q_off / q_len) whose dQ / dK / dV leave

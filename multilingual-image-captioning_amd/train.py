@@ -515,7 +515,9 @@ class Trainer:
                  fp8_scaling: str = "delayed", pack_rows: bool = True, comm_cus: Optional[int] = None, emulate_comm: int = 0,
                  fp8_head: Optional[str] = None, accumulate_steps: int = 1, max_grad_norm: Optional[float] = None):
         """pack_rows (bfloat16 mode, with compact_head): the decoder runs on the valid caption positions only (`packed_rows`);
-        exact — padded positions neither carry loss nor are attended to — and ~1/3 fewer decoder rows on ragged captions.  Needs
+        exact — padded positions neither carry loss nor are attended to — and ~1/3 fewer decoder rows on ragged captions at seq 64,
+        nearly half at seq 128.  Any seq_len up to max_position_embeddings and any number of encoder positions: beyond one 64x64
+        attention tile the tiled attention kernels take the packed rows (`ops.attn_*_packed_tiled`).  Needs
         prefix-shaped masks available on the host: a numpy / CPU `attention_mask`, or `batch["packed_rows"]` from the collate
         function; otherwise the step runs padded.  MIC_PACK_ROWS=0 switches it off.
         grad_comm_dtype: None / torch.float32 (default: the reference's fp32 `lax.pmean`, main.py:698), torch.bfloat16 (opt-in: half
@@ -820,10 +822,10 @@ class Trainer:
                     pk = packed_rows(am, di.cpu().numpy() if isinstance(di, torch.Tensor) else np.asarray(di))
             if 0 < idx.numel() < B * T:
                 rows, row_labels = (idx, int(idx.numel())), rl
-        # packed decoder rows: bf16-storage kernels, one attention tile per sequence, compacted head on the same rows
+        # packed decoder rows: bf16-storage kernels, compacted head on the same rows (any seq_len, any number of encoder positions)
         self._pack = None
         eng = m.engine
-        if pk is not None and rows is not None and eng.dt == torch.bfloat16 and T <= 64 and m.store.S <= 64:
+        if pk is not None and rows is not None and eng.dt == torch.bfloat16:
             ql = pk[1]
             if not (isinstance(ql, torch.Tensor) and ql.is_cuda):
                 # host-side description: it must describe the same positions as `loss_rows` (a collate function that built the two
