@@ -675,119 +675,114 @@ extern "C" int mic_attn_probs(int dtype, int B, int H, int Tq, int Tk, const voi
   return MIC_OK;
 }
 
+// ------------------------------------------------------------------ host side of the four training cores
+// One description of a call, one argument check and one launcher per direction.  The seven entry points below fill an AttnCall, state
+// their own limits and say which cores take the call: tiled (64-row blocks, any Tq / Tk) or one 64x64 tile per sequence.
+struct AttnCall {
+  void* stream;
+  int dtype, B, H, Tq, Tk;  // packed rows: Tq is Tq_max
+  PackedRows pk;            // dense rows: all zero
+  const void* q; int ldq;
+  const void* k; int ldk;
+  const void* v; int ldv;
+  const void* out; int ldo;  // out and lse: written by forward, read by backward
+  const int32_t* key_mask; int causal;
+  const float* lse;
+  const void* dout; int lddo;  // from here on backward only
+  void* dq; int lddq;
+  void* dk; int lddk;
+  void* dv; int lddv;
+  Q8Out q8q, q8kv;  // filled: dQ and dK | dV leave as fp8 bytes (bf16 storage, one tile: mic_attn_bwd_q8)
+};
+
+enum : unsigned { ATTN_BWD = 1, ATTN_PACKED = 2, ATTN_ONE_TILE = 4, ATTN_KV_IS_Q = 8 };  // what an entry point requires of its call
+
+static int attn_check(const char* fn, const AttnCall& c, unsigned need) {
+  const bool dims = c.B > 0 && c.H > 0 && c.Tq > 0 && c.Tk > 0, bwd = need & ATTN_BWD;
+  if (need & ATTN_ONE_TILE) MIC_CHECK(dims && c.Tq <= 64 && c.Tk <= 64, "%s: one 64x64 tile per sequence (Tq=%d Tk=%d)", fn, c.Tq, c.Tk);
+  MIC_CHECK(dims, "%s: bad shape B=%d H=%d Tq=%d Tk=%d", fn, c.B, c.H, c.Tq, c.Tk);
+  MIC_CHECK(c.q && c.k && c.v && c.out && (!bwd || (c.dout && c.lse && c.dq && c.dk && c.dv)) &&
+                (!(need & ATTN_PACKED) || (c.pk.q_off && c.pk.q_len)), "%s: null pointer", fn);
+  MIC_CHECK(c.dtype == MIC_BF16 || c.dtype == MIC_F32, "%s: bad dtype", fn);
+  if (need & ATTN_KV_IS_Q)  // the keys ARE the packed rows
+    MIC_CHECK(!c.pk.kv_packed || c.Tk == c.Tq, "%s: kv_packed needs Tk == Tq_max (Tq_max=%d Tk=%d)", fn, c.Tq, c.Tk);
+  const int align = c.dtype == MIC_BF16 ? 8 : 4;
+  MIC_CHECK(c.ldq % align == 0 && c.ldk % align == 0 && c.ldv % align == 0 && (!bwd || (c.ldo % align == 0 && c.lddo % align == 0)),
+            "%s: row strides must keep 16-B alignment", fn);
+  return MIC_OK;
+}
+
+template <typename T>
+static int launch_fwd(const AttnCall& c, bool tiled) {
+  const auto kernel = tiled ? attn_fwd_tiled_kernel<T> : attn_fwd_kernel<T>;
+  const size_t lds = tiled ? 4 * Tile<T>::BYTES + 2048 : 4 * Tile<T>::BYTES + 1024;
+  if (int rc = set_lds(kernel, lds)) return rc;
+  dim3 grid(c.B * c.H * (tiled ? (c.Tq + 63) / 64 : 1)), block(256);
+  hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)c.stream, c.H, c.Tq, c.Tk, (const T*)c.q, c.ldq, (const T*)c.k, c.ldk, (const T*)c.v,
+                     c.ldv, (T*)c.out, c.ldo, c.key_mask, c.causal, (float*)c.lse, c.pk);
+  MIC_LAUNCH_CHECK();
+  return MIC_OK;
+}
+static int attn_forward(const AttnCall& c, bool tiled) {
+  return c.dtype == MIC_BF16 ? launch_fwd<uint16_t>(c, tiled) : launch_fwd<float>(c, tiled);
+}
+
+template <typename T, bool Q8>
+static int launch_bwd(const AttnCall& c, bool tiled) {
+  auto launch = [&c](auto kernel, int blocks, size_t lds, auto... q8) -> int {
+    if (int rc = set_lds(kernel, lds)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds, (hipStream_t)c.stream, c.H, c.Tq, c.Tk, (const T*)c.q, c.ldq, (const T*)c.k, c.ldk,
+                       (const T*)c.v, c.ldv, (const T*)c.out, c.ldo, (const T*)c.dout, c.lddo, c.lse, c.key_mask, c.causal, (T*)c.dq, c.lddq,
+                       (T*)c.dk, c.lddk, (T*)c.dv, c.lddv, c.pk, q8...);
+    return MIC_OK;
+  };
+  if (tiled) {  // two launches: dQ over the query blocks, then dK / dV over the key blocks
+    const size_t lds = 6 * Tile<T>::BYTES + 512;
+    if (int rc = launch(attn_bwd_tiled_kernel<T, 0>, c.B * c.H * ((c.Tq + 63) / 64), lds)) return rc;
+    if (int rc = launch(attn_bwd_tiled_kernel<T, 1>, c.B * c.H * ((c.Tk + 63) / 64), lds)) return rc;
+  } else {
+    if (int rc = launch(attn_bwd_kernel<T, Q8>, c.B * c.H, 5 * Tile<T>::BYTES, c.q8q, c.q8kv)) return rc;
+  }
+  MIC_LAUNCH_CHECK();
+  return MIC_OK;
+}
+static int attn_backward(const AttnCall& c, bool tiled) {
+  if (c.dtype != MIC_BF16) return launch_bwd<float, false>(c, tiled);
+  return c.q8q.q ? launch_bwd<uint16_t, true>(c, tiled) : launch_bwd<uint16_t, false>(c, tiled);
+}
+
 extern "C" int mic_attn_fwd(int dtype, int B, int H, int Tq, int Tk, const void* q, int ldq, const void* k, int ldk,
                             const void* v, int ldv, void* out, int ldo, const int32_t* key_mask, int causal, float* lse,
                             void* stream) {
-  MIC_CHECK(B > 0 && H > 0 && Tq > 0 && Tk > 0, "mic_attn_fwd: bad shape B=%d H=%d Tq=%d Tk=%d", B, H, Tq, Tk);
-  MIC_CHECK(q && k && v && out, "mic_attn_fwd: null pointer");
-  const int align = dtype == MIC_BF16 ? 8 : 4;
-  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0, "mic_attn_fwd: row strides must keep 16-B alignment");
-  if (Tq > 64 || Tk > 64) {  // online-softmax walk over 64-key blocks
-    dim3 grid(B * H * ((Tq + 63) / 64)), block(256);
-    if (dtype == MIC_BF16) {
-      hipLaunchKernelGGL(attn_fwd_tiled_kernel<uint16_t>, grid, block, 4 * Tile<uint16_t>::BYTES + 2048, (hipStream_t)stream, H, Tq, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)out, ldo, key_mask, causal, lse, PackedRows{nullptr, nullptr, 0});
-    } else if (dtype == MIC_F32) {
-      const size_t lds = 4 * Tile<float>::BYTES + 2048;
-      if (int rc = set_lds(attn_fwd_tiled_kernel<float>, lds)) return rc;
-      hipLaunchKernelGGL(attn_fwd_tiled_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (float*)out, ldo, key_mask, causal, lse, PackedRows{nullptr, nullptr, 0});
-    } else MIC_CHECK(false, "mic_attn_fwd: bad dtype");
-    MIC_LAUNCH_CHECK();
-    return MIC_OK;
-  }
-  dim3 grid(B * H), block(256);
-  if (dtype == MIC_BF16) {
-    hipLaunchKernelGGL(attn_fwd_kernel<uint16_t>, grid, block, 4 * Tile<uint16_t>::BYTES + 1024, (hipStream_t)stream, H, Tq, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)out, ldo, key_mask, causal, lse, PackedRows{nullptr, nullptr, 0});
-  } else if (dtype == MIC_F32) {
-    const size_t lds = 4 * Tile<float>::BYTES + 1024;
-    if (int rc = set_lds(attn_fwd_kernel<float>, lds)) return rc;
-    hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (float*)out, ldo, key_mask, causal, lse, PackedRows{nullptr, nullptr, 0});
-  } else MIC_CHECK(false, "mic_attn_fwd: bad dtype");
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
+  const AttnCall c{stream, dtype, B, H, Tq, Tk, {}, q, ldq, k, ldk, v, ldv, out, ldo, key_mask, causal, lse};
+  if (int rc = attn_check("mic_attn_fwd", c, 0)) return rc;
+  return attn_forward(c, Tq > 64 || Tk > 64);
 }
-
-// the two launches of the tiled backward: dQ over the query blocks, then dK / dV over the key blocks
-template <typename TT>
-static int launch_bwd_tiled(int B, int H, int Tq, int Tk, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out,
-                            int ldo, const void* dout, int lddo, const float* lse, const int32_t* key_mask, int causal, void* dq, int lddq,
-                            void* dk, int lddk, void* dv, int lddv, PackedRows pk, void* stream) {
-  dim3 gq(B * H * ((Tq + 63) / 64)), gk(B * H * ((Tk + 63) / 64)), block(256);
-  const size_t lds = 6 * Tile<TT>::BYTES + 512;
-  if (int rc = set_lds(attn_bwd_tiled_kernel<TT, 0>, lds)) return rc;
-  if (int rc = set_lds(attn_bwd_tiled_kernel<TT, 1>, lds)) return rc;
-  hipLaunchKernelGGL((attn_bwd_tiled_kernel<TT, 0>), gq, block, lds, (hipStream_t)stream, H, Tq, Tk, (const TT*)q, ldq, (const TT*)k, ldk, (const TT*)v, ldv, (const TT*)out, ldo, (const TT*)dout, lddo, lse, key_mask, causal, (TT*)dq, lddq, (TT*)dk, lddk, (TT*)dv, lddv, pk);
-  hipLaunchKernelGGL((attn_bwd_tiled_kernel<TT, 1>), gk, block, lds, (hipStream_t)stream, H, Tq, Tk, (const TT*)q, ldq, (const TT*)k, ldk, (const TT*)v, ldv, (const TT*)out, ldo, (const TT*)dout, lddo, lse, key_mask, causal, (TT*)dq, lddq, (TT*)dk, lddk, (TT*)dv, lddv, pk);
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
-}
-
 extern "C" int mic_attn_bwd(int dtype, int B, int H, int Tq, int Tk, const void* q, int ldq, const void* k, int ldk,
                             const void* v, int ldv, const void* out, int ldo, const void* dout, int lddo, const float* lse,
                             const int32_t* key_mask, int causal, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv,
                             void* stream) {
-  MIC_CHECK(B > 0 && H > 0 && Tq > 0 && Tk > 0, "mic_attn_bwd: bad shape");
-  MIC_CHECK(q && k && v && out && dout && lse && dq && dk && dv, "mic_attn_bwd: null pointer");
-  const int align = dtype == MIC_BF16 ? 8 : 4;
-  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0 && ldo % align == 0 && lddo % align == 0, "mic_attn_bwd: row strides must keep 16-B alignment");
-  if (Tq > 64 || Tk > 64) {
-    MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_attn_bwd: bad dtype");
-    const PackedRows pk{nullptr, nullptr, 0};
-    return dtype == MIC_BF16 ? launch_bwd_tiled<uint16_t>(B, H, Tq, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, key_mask, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream)
-                             : launch_bwd_tiled<float>(B, H, Tq, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, key_mask, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream);
-  }
-  dim3 grid(B * H), block(256);
-  if (dtype == MIC_BF16) {
-    const size_t lds = 5 * Tile<uint16_t>::BYTES;
-    hipLaunchKernelGGL(attn_bwd_kernel<uint16_t>, grid, block, lds, (hipStream_t)stream, H, Tq, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (const uint16_t*)out, ldo, (const uint16_t*)dout, lddo, lse, key_mask, causal, (uint16_t*)dq, lddq, (uint16_t*)dk, lddk, (uint16_t*)dv, lddv, PackedRows{nullptr, nullptr, 0}, Q8Out{}, Q8Out{});
-  } else if (dtype == MIC_F32) {
-    const size_t lds = 5 * Tile<float>::BYTES;
-    if (int rc = set_lds(attn_bwd_kernel<float>, lds)) return rc;
-    hipLaunchKernelGGL(attn_bwd_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (const float*)out, ldo, (const float*)dout, lddo, lse, key_mask, causal, (float*)dq, lddq, (float*)dk, lddk, (float*)dv, lddv, PackedRows{nullptr, nullptr, 0}, Q8Out{}, Q8Out{});
-  } else MIC_CHECK(false, "mic_attn_bwd: bad dtype");
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
+  const AttnCall c{stream, dtype, B, H, Tq, Tk, {}, q, ldq, k, ldk, v, ldv, out, ldo, key_mask, causal, lse, dout, lddo, dq, lddq, dk, lddk, dv, lddv};
+  if (int rc = attn_check("mic_attn_bwd", c, ATTN_BWD)) return rc;
+  return attn_backward(c, Tq > 64 || Tk > 64);
 }
 
 // ------------------------------------------------------------------ packed (variable-length) rows, one 64x64 tile per sequence
 extern "C" int mic_attn_fwd_packed(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
                                    const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
                                    int causal, float* lse, void* stream) {
-  MIC_CHECK(B > 0 && H > 0 && Tq_max > 0 && Tq_max <= 64 && Tk > 0 && Tk <= 64, "mic_attn_fwd_packed: one 64x64 tile per sequence (Tq_max=%d Tk=%d)", Tq_max, Tk);
-  MIC_CHECK(q && k && v && out && q_off && q_len, "mic_attn_fwd_packed: null pointer");
-  const int align = dtype == MIC_BF16 ? 8 : 4;
-  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0, "mic_attn_fwd_packed: row strides must keep 16-B alignment");
-  const PackedRows pk{q_off, q_len, kv_packed};
-  dim3 grid(B * H), block(256);
-  if (dtype == MIC_BF16) {
-    hipLaunchKernelGGL(attn_fwd_kernel<uint16_t>, grid, block, 4 * Tile<uint16_t>::BYTES + 1024, (hipStream_t)stream, H, Tq_max, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)out, ldo, nullptr, causal, lse, pk);
-  } else if (dtype == MIC_F32) {
-    const size_t lds = 4 * Tile<float>::BYTES + 1024;
-    if (int rc = set_lds(attn_fwd_kernel<float>, lds)) return rc;
-    hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq_max, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (float*)out, ldo, nullptr, causal, lse, pk);
-  } else MIC_CHECK(false, "mic_attn_fwd_packed: bad dtype");
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
+  const AttnCall c{stream, dtype, B, H, Tq_max, Tk, {q_off, q_len, kv_packed}, q, ldq, k, ldk, v, ldv, out, ldo, nullptr, causal, lse};
+  if (int rc = attn_check("mic_attn_fwd_packed", c, ATTN_PACKED | ATTN_ONE_TILE)) return rc;
+  return attn_forward(c, false);
 }
 extern "C" int mic_attn_bwd_packed(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
                                    const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
                                    const void* dout, int lddo, const float* lse, int causal, void* dq, int lddq, void* dk, int lddk,
                                    void* dv, int lddv, void* stream) {
-  MIC_CHECK(B > 0 && H > 0 && Tq_max > 0 && Tq_max <= 64 && Tk > 0 && Tk <= 64, "mic_attn_bwd_packed: one 64x64 tile per sequence (Tq_max=%d Tk=%d)", Tq_max, Tk);
-  MIC_CHECK(q && k && v && out && dout && lse && dq && dk && dv && q_off && q_len, "mic_attn_bwd_packed: null pointer");
-  const int align = dtype == MIC_BF16 ? 8 : 4;
-  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0 && ldo % align == 0 && lddo % align == 0, "mic_attn_bwd_packed: row strides must keep 16-B alignment");
-  const PackedRows pk{q_off, q_len, kv_packed};
-  dim3 grid(B * H), block(256);
-  if (dtype == MIC_BF16) {
-    const size_t lds = 5 * Tile<uint16_t>::BYTES;
-    hipLaunchKernelGGL(attn_bwd_kernel<uint16_t>, grid, block, lds, (hipStream_t)stream, H, Tq_max, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (const uint16_t*)out, ldo, (const uint16_t*)dout, lddo, lse, nullptr, causal, (uint16_t*)dq, lddq, (uint16_t*)dk, lddk, (uint16_t*)dv, lddv, pk, Q8Out{}, Q8Out{});
-  } else if (dtype == MIC_F32) {
-    const size_t lds = 5 * Tile<float>::BYTES;
-    if (int rc = set_lds(attn_bwd_kernel<float>, lds)) return rc;
-    hipLaunchKernelGGL(attn_bwd_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq_max, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (const float*)out, ldo, (const float*)dout, lddo, lse, nullptr, causal, (float*)dq, lddq, (float*)dk, lddk, (float*)dv, lddv, pk, Q8Out{}, Q8Out{});
-  } else MIC_CHECK(false, "mic_attn_bwd_packed: bad dtype");
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
+  const AttnCall c{stream, dtype, B, H, Tq_max, Tk, {q_off, q_len, kv_packed}, q, ldq, k, ldk, v, ldv, out, ldo, nullptr, causal, lse, dout, lddo,
+                   dq, lddq, dk, lddk, dv, lddv};
+  if (int rc = attn_check("mic_attn_bwd_packed", c, ATTN_BWD | ATTN_PACKED | ATTN_ONE_TILE)) return rc;
+  return attn_backward(c, false);
 }
 
 // ------------------------------------------------------------------ packed rows, any length: always the tiled kernels
@@ -796,37 +791,18 @@ extern "C" int mic_attn_bwd_packed(int dtype, int B, int H, int Tq_max, int Tk, 
 extern "C" int mic_attn_fwd_packed_tiled(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
                                          const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
                                          int causal, float* lse, void* stream) {
-  MIC_CHECK(B > 0 && H > 0 && Tq_max > 0 && Tk > 0, "mic_attn_fwd_packed_tiled: bad shape B=%d H=%d Tq_max=%d Tk=%d", B, H, Tq_max, Tk);
-  MIC_CHECK(q && k && v && out && q_off && q_len, "mic_attn_fwd_packed_tiled: null pointer");
-  MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_attn_fwd_packed_tiled: bad dtype");
-  MIC_CHECK(!kv_packed || Tk == Tq_max, "mic_attn_fwd_packed_tiled: kv_packed needs Tk == Tq_max (Tq_max=%d Tk=%d)", Tq_max, Tk);
-  const int align = dtype == MIC_BF16 ? 8 : 4;
-  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0, "mic_attn_fwd_packed_tiled: row strides must keep 16-B alignment");
-  const PackedRows pk{q_off, q_len, kv_packed};
-  dim3 grid(B * H * ((Tq_max + 63) / 64)), block(256);
-  if (dtype == MIC_BF16) {
-    hipLaunchKernelGGL(attn_fwd_tiled_kernel<uint16_t>, grid, block, 4 * Tile<uint16_t>::BYTES + 2048, (hipStream_t)stream, H, Tq_max, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, (uint16_t*)out, ldo, nullptr, causal, lse, pk);
-  } else {
-    const size_t lds = 4 * Tile<float>::BYTES + 2048;
-    if (int rc = set_lds(attn_fwd_tiled_kernel<float>, lds)) return rc;
-    hipLaunchKernelGGL(attn_fwd_tiled_kernel<float>, grid, block, lds, (hipStream_t)stream, H, Tq_max, Tk, (const float*)q, ldq, (const float*)k, ldk, (const float*)v, ldv, (float*)out, ldo, nullptr, causal, lse, pk);
-  }
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
+  const AttnCall c{stream, dtype, B, H, Tq_max, Tk, {q_off, q_len, kv_packed}, q, ldq, k, ldk, v, ldv, out, ldo, nullptr, causal, lse};
+  if (int rc = attn_check("mic_attn_fwd_packed_tiled", c, ATTN_PACKED | ATTN_KV_IS_Q)) return rc;
+  return attn_forward(c, true);
 }
 extern "C" int mic_attn_bwd_packed_tiled(int dtype, int B, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len, int kv_packed,
                                          const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
                                          const void* dout, int lddo, const float* lse, int causal, void* dq, int lddq, void* dk, int lddk,
                                          void* dv, int lddv, void* stream) {
-  MIC_CHECK(B > 0 && H > 0 && Tq_max > 0 && Tk > 0, "mic_attn_bwd_packed_tiled: bad shape B=%d H=%d Tq_max=%d Tk=%d", B, H, Tq_max, Tk);
-  MIC_CHECK(q && k && v && out && dout && lse && dq && dk && dv && q_off && q_len, "mic_attn_bwd_packed_tiled: null pointer");
-  MIC_CHECK(dtype == MIC_BF16 || dtype == MIC_F32, "mic_attn_bwd_packed_tiled: bad dtype");
-  MIC_CHECK(!kv_packed || Tk == Tq_max, "mic_attn_bwd_packed_tiled: kv_packed needs Tk == Tq_max (Tq_max=%d Tk=%d)", Tq_max, Tk);
-  const int align = dtype == MIC_BF16 ? 8 : 4;
-  MIC_CHECK(ldq % align == 0 && ldk % align == 0 && ldv % align == 0 && ldo % align == 0 && lddo % align == 0, "mic_attn_bwd_packed_tiled: row strides must keep 16-B alignment");
-  const PackedRows pk{q_off, q_len, kv_packed};
-  return dtype == MIC_BF16 ? launch_bwd_tiled<uint16_t>(B, H, Tq_max, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, nullptr, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream)
-                           : launch_bwd_tiled<float>(B, H, Tq_max, Tk, q, ldq, k, ldk, v, ldv, out, ldo, dout, lddo, lse, nullptr, causal, dq, lddq, dk, lddk, dv, lddv, pk, stream);
+  const AttnCall c{stream, dtype, B, H, Tq_max, Tk, {q_off, q_len, kv_packed}, q, ldq, k, ldk, v, ldv, out, ldo, nullptr, causal, lse, dout, lddo,
+                   dq, lddq, dk, lddk, dv, lddv};
+  if (int rc = attn_check("mic_attn_bwd_packed_tiled", c, ATTN_BWD | ATTN_PACKED | ATTN_KV_IS_Q)) return rc;
+  return attn_backward(c, true);
 }
 
 // fused fp8 emission of dQ / dK / dV (bf16 storage, one 64x64 tile per sequence; dense rows with q_off == NULL, packed rows otherwise)
@@ -834,20 +810,14 @@ extern "C" int mic_attn_bwd_q8(int B, int H, int Tq, int Tk, const int32_t* q_of
                                int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo, const void* dout, int lddo,
                                const float* lse, const int32_t* key_mask, int causal, const mic_fp8_out* dq8, const mic_fp8_out* dk8,
                                void* dv8, void* stream) {
-  MIC_CHECK(B > 0 && H > 0 && Tq > 0 && Tq <= 64 && Tk > 0 && Tk <= 64, "mic_attn_bwd_q8: one 64x64 tile per sequence (Tq=%d Tk=%d)", Tq, Tk);
-  MIC_CHECK(q && k && v && out && dout && lse && dq8 && dk8 && dv8 && (!q_off == !q_len), "mic_attn_bwd_q8: null pointer");
+  MIC_CHECK(dq8 && dk8 && dv8 && (!q_off == !q_len), "mic_attn_bwd_q8: null pointer");
   MIC_CHECK(dq8->q && dq8->state && dk8->q && dk8->state && dq8->fmt == dk8->fmt && (dq8->fmt == MIC_E4M3 || dq8->fmt == MIC_E5M2),
             "mic_attn_bwd_q8: bad fp8 outputs");
-  MIC_CHECK(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0, "mic_attn_bwd_q8: row strides must keep 16-B alignment");
-  const PackedRows pk{q_off, q_len, kv_packed};
   const Q8Out oq{(uint8_t*)dq8->q, dq8->ldq, dq8->state, dq8->amax_next, dq8->fmt}, okv{(uint8_t*)dk8->q, dk8->ldq, dk8->state, dk8->amax_next, dk8->fmt};
-  dim3 grid(B * H), block(256);
-  const size_t lds = 5 * Tile<uint16_t>::BYTES;
-  hipLaunchKernelGGL((attn_bwd_kernel<uint16_t, true>), grid, block, lds, (hipStream_t)stream, H, Tq, Tk, (const uint16_t*)q, ldq, (const uint16_t*)k, ldk,
-                     (const uint16_t*)v, ldv, (const uint16_t*)out, ldo, (const uint16_t*)dout, lddo, lse, key_mask, causal, (uint16_t*)dq8->q, dq8->ldq,
-                     (uint16_t*)dk8->q, dk8->ldq, (uint16_t*)dv8, dk8->ldq, pk, oq, okv);
-  MIC_LAUNCH_CHECK();
-  return MIC_OK;
+  const AttnCall c{stream, MIC_BF16, B, H, Tq, Tk, {q_off, q_len, kv_packed}, q, ldq, k, ldk, v, ldv, out, ldo, key_mask, causal, lse, dout, lddo,
+                   dq8->q, dq8->ldq, dk8->q, dk8->ldq, dv8, dk8->ldq, oq, okv};
+  if (int rc = attn_check("mic_attn_bwd_q8", c, ATTN_BWD | ATTN_ONE_TILE)) return rc;
+  return attn_backward(c, false);
 }
 
 // 8 cache elements as they arrive from memory (converted at use: a load in flight costs 4 registers in bf16)

@@ -34,7 +34,9 @@ def _mix(seed: int, site: int) -> int:
 def packed_attn_tiled(Tq_max: int, Tk: int) -> bool:
     """which packed attention cores one call takes: the one-tile kernels while queries and keys fit one 64x64 tile, the tiled ones
     (`ops.attn_*_packed_tiled`) beyond.  Self-attention asks with (T, T), cross-attention with (T, S): at T <= 64 < S only the
-    cross-attention leaves the one-tile kernels."""
+    cross-attention leaves the one-tile kernels.
+    This is the engine's one-tile rule for packed and dense rows alike: `Engine.attn_forward` / `attn_backward` choose by it, and fp8
+    emission out of the attention backward (`dy8_target` of its q/k/v projections) is asked for only where it answers False."""
     return Tq_max > 64 or Tk > 64
 
 
@@ -192,6 +194,35 @@ class Engine(Fp8Views):
         self._ET_version, self._ET_event, self._head_nt_state = -1, None, None
         self._lnf = {}
         self._lnf_version = -1
+
+    # ------------------------------------------------------------------ attention cores: which entry point takes a call
+    def attn_forward(self, q, k, v, out, lse, B, H, Tq, Tk, *, ldq, ldk, ldv, ldo, pack=None, kv_packed=False, key_mask=None, causal=False):
+        """out, lse = attention of q over k / v.  pack = (q_off, q_len, rows) or None: packed query rows take the packed cores (one-tile
+        or tiled by `packed_attn_tiled`), which know no key mask — every position of a packed sequence is valid; kv_packed: the keys
+        are those packed rows too (self-attention), not [B][Tk] rows (cross-attention)."""
+        if pack is None:
+            ops.attn_fwd(q, k, v, out, B, H, Tq, Tk, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, key_mask=key_mask, causal=causal, lse=lse)
+        else:
+            fwd = ops.attn_fwd_packed_tiled if packed_attn_tiled(Tq, Tk) else ops.attn_fwd_packed
+            fwd(q, k, v, out, B, H, Tq, Tk, pack[0], pack[1], kv_packed=kv_packed, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, causal=causal, lse=lse)
+
+    def attn_backward(self, q, k, v, out, dout, lse, B, H, Tq, Tk, *, ldq, ldk, ldv, ldo, lddo, grads=None, ldg=None, grads8=None, pack=None,
+                      kv_packed=False, key_mask=None, causal=False):
+        """the backward of `attn_forward` (same pack / kv_packed / key_mask / causal).  Either grads = (dq, dk, dv) with their row strides
+        ldg, or grads8 = (dQ's `fp8_out`, dK's `fp8_out`, dV's fp8 view): the gradients leave as fp8 bytes, one 64x64 tile only."""
+        q_off, q_len = (None, None) if pack is None else pack[:2]
+        if grads8 is not None:
+            if packed_attn_tiled(Tq, Tk):
+                raise ValueError(f"attention backward: fp8 emission needs one 64x64 tile per sequence (Tq={Tq} Tk={Tk})")
+            ops.attn_bwd_q8(q, k, v, out, dout, lse, *grads8, B, H, Tq, Tk, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, lddo=lddo, q_off=q_off, q_len=q_len,
+                            kv_packed=kv_packed and pack is not None, key_mask=key_mask if pack is None else None, causal=causal)
+            return
+        ld = dict(ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, lddo=lddo, lddq=ldg[0], lddk=ldg[1], lddv=ldg[2])
+        if pack is None:
+            ops.attn_bwd(q, k, v, out, dout, lse, *grads, B, H, Tq, Tk, key_mask=key_mask, causal=causal, **ld)
+        else:
+            bwd = ops.attn_bwd_packed_tiled if packed_attn_tiled(Tq, Tk) else ops.attn_bwd_packed
+            bwd(q, k, v, out, dout, lse, *grads, B, H, Tq, Tk, q_off, q_len, kv_packed=kv_packed, causal=causal, **ld)
 
     # ------------------------------------------------------------------ small helpers
     def linear(self, x, wname, out, M, *, act=0, zout=None, residual=None, drop_seed=None, bias=True, save_tag=None, fp8=True,
@@ -441,7 +472,7 @@ class Engine(Fp8Views):
             self.linear(a1, p + "qkv", qkv, Mv, save_tag=tag if save else None, x8=a1_8)
             ctx = self.buf(tag + "ctx", Mv, vd)
             lse = self.vec(tag + "lse", B * H * S)
-            ops.attn_fwd(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, B, H, S, S, ldq=3 * vd, ldk=3 * vd, ldv=3 * vd, ldo=vd, lse=lse)
+            self.attn_forward(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, lse, B, H, S, S, ldq=3 * vd, ldk=3 * vd, ldv=3 * vd, ldo=vd)
             xm = self.buf(tag + "xm", Mv, vd)
             self.linear(ctx, p + "o", xm, Mv, residual=x)
             st2 = self.buf(tag + "st2", 2, _rup(Mv, ROWPAD), torch.float32)
@@ -492,17 +523,16 @@ class Engine(Fp8Views):
             self.ln_bwd("v2", l, xm, p + "ln2", st2[0], st2[1], da, dxm, Mv, dres=dx)
             dctx = self.buf("vb.dctx", Mv, vd)
             self.linear_bwd(p + "o", ctx, dxm, Mv, dx=dctx, defer=True)
-            dq8t = self.dy8_target(p + "qkv", self._par(l), Mv) if S <= 64 else None
+            dq8t = None if packed_attn_tiled(S, S) else self.dy8_target(p + "qkv", self._par(l), Mv)
             if dq8t is not None:
-                q8 = dq8t.q
-                ops.attn_bwd_q8(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, dctx, lse, dq8t.out, dq8t.view(q8[:, vd:]).out, q8[:, 2 * vd:],
-                                B, H, S, S, ldq=3 * vd, ldk=3 * vd, ldv=3 * vd, ldo=vd, lddo=vd)
-                self.linear_bwd(p + "qkv", a1, None, Mv, dx=da, defer=True, dy8=dq8t.q8, par=self._par(l))
+                dqkv, q8 = None, dq8t.q
+                grads = dict(grads8=(dq8t.out, dq8t.view(q8[:, vd:]).out, q8[:, 2 * vd:]))
             else:
                 dqkv = self.dyb("vb.dqkv", l, Mv, 3 * vd)
-                ops.attn_bwd(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, dctx, lse, dqkv, dqkv[:, vd:], dqkv[:, 2 * vd:], B, H, S, S,
-                             ldq=3 * vd, ldk=3 * vd, ldv=3 * vd, ldo=vd, lddo=vd, lddq=3 * vd, lddk=3 * vd, lddv=3 * vd)
-                self.linear_bwd(p + "qkv", a1, dqkv, Mv, dx=da, defer=True, par=self._par(l))
+                grads = dict(grads=(dqkv, dqkv[:, vd:], dqkv[:, 2 * vd:]), ldg=(3 * vd, 3 * vd, 3 * vd))
+            self.attn_backward(qkv, qkv[:, vd:], qkv[:, 2 * vd:], ctx, dctx, lse, B, H, S, S, ldq=3 * vd, ldk=3 * vd, ldv=3 * vd, ldo=vd, lddo=vd,
+                               **grads)
+            self.linear_bwd(p + "qkv", a1, dqkv, Mv, dx=da, defer=True, dy8=None if dq8t is None else dq8t.q8, par=self._par(l))
             flush_now = self._dw_flush_layer(l)
             late = self.dw_fence() if flush_now else False
             if flush_now and not late:
@@ -563,13 +593,8 @@ class Engine(Fp8Views):
             self.linear(a, p + "qkv", qkv, M, save_tag=tag if save else None, x8=a8)
             ctx = self.buf(tag + "ctx", Mcap, d)
             lse = self.vec(tag + "lse", B * H * T)
-            if pack is not None:
-                fwd_packed = ops.attn_fwd_packed_tiled if packed_attn_tiled(T, T) else ops.attn_fwd_packed
-                fwd_packed(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, B, H, T, T, pack[0], pack[1], kv_packed=True, ldq=3 * d, ldk=3 * d,
-                           ldv=3 * d, ldo=d, causal=True, lse=lse)
-            else:
-                ops.attn_fwd(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, B, H, T, T, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, key_mask=key_mask,
-                             causal=True, lse=lse)
+            self.attn_forward(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, lse, B, H, T, T, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, pack=pack,
+                              kv_packed=True, key_mask=key_mask, causal=True)
             x1 = self.buf(tag + "x1", Mcap, d)
             self.linear(ctx, p + "so", x1, M, residual=x, drop_seed=sd(10 + 3 * l))
             a, a8 = self.ln_q8(x1, p + "ln_ca", self.dec_eps, tag + "a_ca", Mcap, stats[2], stats[3], M, p + "cq", tag)
@@ -582,11 +607,7 @@ class Engine(Fp8Views):
                 self.linear(ehs, p + "ckv", kv, Mv, save_tag="d.ehs." if save else None, stable_input=True)
             cctx = self.buf(tag + "cctx", Mcap, d)
             clse = self.vec(tag + "clse", B * H * T)
-            if pack is not None:
-                fwd_packed = ops.attn_fwd_packed_tiled if packed_attn_tiled(T, S) else ops.attn_fwd_packed
-                fwd_packed(q, kv, kv[:, d:], cctx, B, H, T, S, pack[0], pack[1], kv_packed=False, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lse=clse)
-            else:
-                ops.attn_fwd(q, kv, kv[:, d:], cctx, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lse=clse)
+            self.attn_forward(q, kv, kv[:, d:], cctx, clse, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, pack=pack)
             x2 = self.buf(tag + "x2", Mcap, d)
             self.linear(cctx, p + "co", x2, M, residual=x1, drop_seed=sd(11 + 3 * l))
             a, a8 = self.ln_q8(x2, p + "ln_ff", self.dec_eps, tag + "a_ff", Mcap, stats[4], stats[5], M, p + "fc1", tag)
@@ -779,7 +800,7 @@ class Engine(Fp8Views):
         kvcat = self.buf("d.ckvcat", Mv, P.L * 2 * d) if hoist else None
         hoist8 = hoist and f8 is not None and "ckvcat" in f8.weights
         # fp8, hoisted: every layer's dK | dV lands in its column slice of ONE e5m2 matrix under one scale (fused emission) ...
-        dkvcat8t = f8.target("ckvcat.dy", "f8.ckvcat.dy", Mv, P.L * 2 * d, E5M2) if (hoist8 and T <= 64 and S <= 64) else None
+        dkvcat8t = f8.target("ckvcat.dy", "f8.ckvcat.dy", Mv, P.L * 2 * d, E5M2) if (hoist8 and not packed_attn_tiled(T, S)) else None
         # ... or, without a scale history, in the bf16 matrix that is quantised once behind the loop
         dkvcat = self.buf("db.dkvcat", Mv, P.L * 2 * d) if (hoist and dkvcat8t is None) else None
         for l in reversed(range(P.L)):
@@ -807,7 +828,7 @@ class Engine(Fp8Views):
             # --- cross-attention branch
             dctx = self.buf("db.dctx", Mcap, d)
             self.linear_bwd(p + "co", cctx, dxm_b, M, dx=dctx, defer=True)
-            one_tile = T <= 64 and S <= 64
+            one_tile = not packed_attn_tiled(T, S)
             dq8t = self.dy8_target(p + "cq", self._par(l), Mcap) if one_tile else None
             if hoist:
                 dkv8t = None if dkvcat8t is None else dkvcat8t.view(dkvcat8t.q[:, l * 2 * d:])
@@ -815,51 +836,34 @@ class Engine(Fp8Views):
                 dkv8t = self.dy8_target(p + "ckv", self._par(l), Mv) if one_tile else None
             if dq8t is not None and dkv8t is not None:
                 # dQ [rows][d] and dK | dV [encoder rows][2d] as e5m2 bytes under their own scales, straight out of the attention backward
-                ops.attn_bwd_q8(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq8t.out, dkv8t.out, dkv8t.q[:, d:], B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv,
-                                ldo=d, lddo=d, q_off=pack[0] if pack is not None else None, q_len=pack[1] if pack is not None else None, kv_packed=False)
-                self.linear_bwd(p + "cq", a_ca, None, M, dx=da, defer=True, dy8=dq8t.q8, par=self._par(l))
-                if not hoist:
-                    self.linear_bwd(p + "ckv", ehs, None, Mv, dx=dehs, dx_accumulate=(l != P.L - 1), defer=True, dy8=dkv8t.q8, par=self._par(l))
+                dq, dkv, dq8, dkv8 = None, None, dq8t.q8, dkv8t.q8
+                grads = dict(grads8=(dq8t.out, dkv8t.out, dkv8t.q[:, d:]))
             elif hoist and dkvcat8t is not None:
                 # (dQ has no scale history yet but the concatenated k/v gradient has: cannot happen after the first pass; keep the bytes consistent)
                 raise RuntimeError("fp8: cross-attention dQ without a scale history beside a hoisted k/v gradient with one")
             else:
-                dq = self.dyb("db.dq", l, Mcap, d)
+                dq, dq8, dkv8 = self.dyb("db.dq", l, Mcap, d), None, None
                 dkv = dkvcat[:, l * 2 * d:] if hoist else self.dyb("db.dkv", l, Mv, 2 * d)
-                if pack is not None:
-                    bwd_packed = ops.attn_bwd_packed_tiled if packed_attn_tiled(T, S) else ops.attn_bwd_packed
-                    bwd_packed(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq, dkv, dkv[:, d:], B, H, T, S, pack[0], pack[1], kv_packed=False,
-                               ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lddo=d, lddq=d, lddk=ldkv, lddv=ldkv)
-                else:
-                    ops.attn_bwd(cq, ckv, ckv[:, d:], cctx, dctx, clse, dq, dkv, dkv[:, d:], B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d,
-                                 lddo=d, lddq=d, lddk=ldkv, lddv=ldkv)
-                self.linear_bwd(p + "cq", a_ca, dq, M, dx=da, defer=True, par=self._par(l))
-                if not hoist:
-                    self.linear_bwd(p + "ckv", ehs, dkv, Mv, dx=dehs, dx_accumulate=(l != P.L - 1), defer=True, par=self._par(l))
+                grads = dict(grads=(dq, dkv, dkv[:, d:]), ldg=(d, ldkv, ldkv))
+            self.attn_backward(cq, ckv, ckv[:, d:], cctx, dctx, clse, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lddo=d, pack=pack, **grads)
+            self.linear_bwd(p + "cq", a_ca, dq, M, dx=da, defer=True, dy8=dq8, par=self._par(l))
+            if not hoist:
+                self.linear_bwd(p + "ckv", ehs, dkv, Mv, dx=dehs, dx_accumulate=(l != P.L - 1), defer=True, dy8=dkv8, par=self._par(l))
             dx1 = self.buf("db.dx1", Mcap, d)
             self.ln_bwd("ca", l, x1, p + "ln_ca", stats[2], stats[3], da, dx1, M,
                         dres=dx2, dxm=dxm_c, dropout_p=pd, dropout_seed=sd(10 + 3 * l))
             # --- self-attention branch
             self.linear_bwd(p + "so", ctx, dxm_c, M, dx=dctx, defer=True)
-            dqkv8t = self.dy8_target(p + "qkv", self._par(l), Mcap) if T <= 64 else None
+            dqkv8t = None if packed_attn_tiled(T, T) else self.dy8_target(p + "qkv", self._par(l), Mcap)
             if dqkv8t is not None:
-                q8 = dqkv8t.q
-                ops.attn_bwd_q8(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv8t.out, dqkv8t.view(q8[:, d:]).out, q8[:, 2 * d:],
-                                B, H, T, T, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, q_off=pack[0] if pack is not None else None,
-                                q_len=pack[1] if pack is not None else None, kv_packed=pack is not None,
-                                key_mask=key_mask if pack is None else None, causal=True)
-                self.linear_bwd(p + "qkv", a_sa, None, M, dx=da, defer=True, dy8=dqkv8t.q8, par=self._par(l))
+                dqkv, q8 = None, dqkv8t.q
+                grads = dict(grads8=(dqkv8t.out, dqkv8t.view(q8[:, d:]).out, q8[:, 2 * d:]))
             else:
                 dqkv = self.dyb("db.dqkv", l, Mcap, 3 * d)
-                if pack is not None:
-                    bwd_packed = ops.attn_bwd_packed_tiled if packed_attn_tiled(T, T) else ops.attn_bwd_packed
-                    bwd_packed(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv, dqkv[:, d:], dqkv[:, 2 * d:], B, H, T, T, pack[0],
-                               pack[1], kv_packed=True, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, lddq=3 * d, lddk=3 * d,
-                               lddv=3 * d, causal=True)
-                else:
-                    ops.attn_bwd(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, dqkv, dqkv[:, d:], dqkv[:, 2 * d:], B, H, T, T, ldq=3 * d,
-                                 ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, lddq=3 * d, lddk=3 * d, lddv=3 * d, key_mask=key_mask, causal=True)
-                self.linear_bwd(p + "qkv", a_sa, dqkv, M, dx=da, defer=True, par=self._par(l))
+                grads = dict(grads=(dqkv, dqkv[:, d:], dqkv[:, 2 * d:]), ldg=(3 * d, 3 * d, 3 * d))
+            self.attn_backward(qkv, qkv[:, d:], qkv[:, 2 * d:], ctx, dctx, lse, B, H, T, T, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, lddo=d, pack=pack,
+                               kv_packed=True, key_mask=key_mask, causal=True, **grads)
+            self.linear_bwd(p + "qkv", a_sa, dqkv, M, dx=da, defer=True, dy8=None if dqkv8t is None else dqkv8t.q8, par=self._par(l))
             flush_now = self._dw_flush_layer(l)
             late = self.dw_fence() if flush_now else False
             if flush_now and not late:
