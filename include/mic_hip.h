@@ -180,7 +180,8 @@ int mic_ln_fold_weight(int dtype, int N, int K, const void* w, int ldw, const fl
 /* ---------------------------------------------------------------------------------------------
  * fp8 operands for mic_gemm (BASELINE configs[4]; no reference counterpart — its dtypes are fp32/fp16/bf16, main.py:96-101).
  * Per-tensor current scaling: mic_fp8_amax accumulates state[0] = max |x| (fp32 atomic max; the caller zeroes `state`),
- * mic_fp8_quantize then writes q[r][c] = fp8(x[r][c] * FMAX / amax) (row-major) and / or the transposed copy
+ * mic_fp8_quantize then writes q[r][c] = fp8(x[r][c] * scale), scale = min(FMAX / amax, FLT_MAX) (finite for every amax > 0, so a zero
+ * element always leaves as a zero byte; amax = 0: scale 1), clamped to +-FMAX, round to nearest even (row-major) and / or the transposed copy
  * qT[c][r] (rows zero-padded to rows_pad, so it can be the k-contiguous operand of the weight-gradient GEMM, which reduces
  * over rows), and state[1] = amax / FMAX — the factor mic_gemm multiplies back (a_scale_inv / b_scale_inv).
  * `items` is a HOST array; src is bf16 [rows][ld]; e4m3 (FMAX 448) for activations and weights, e5m2 (FMAX 57344) for gradients.

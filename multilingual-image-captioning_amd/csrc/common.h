@@ -175,11 +175,14 @@ __device__ __forceinline__ uint32_t cvt4_fp8(const float* v, int fmt) {  // 4 fl
   }
   return (uint32_t)w;
 }
+// scale = FMAX / amax, kept finite: the quotient overflows for 0 < amax < FMAX / FLT_MAX (1.3e-36 for e4m3, 1.7e-34 for e5m2 — normal
+// bf16 values), and an infinite scale turns every zero element into NaN, which the clamp below sends out as the -FMAX byte
+__device__ __forceinline__ float q8_scale(float fmax, float amax) { return amax > 0.f ? fminf(fmax / amax, 3.402823466e+38f) : 1.0f; }
 __device__ __forceinline__ Q8Ctx q8_begin(const Q8Out& o, bool first_thread) {
   Q8Ctx c;
   c.fmax = o.fmt == MIC_E4M3 ? 448.0f : 57344.0f;
   const float amax = o.state[0];
-  c.scale = amax > 0.f ? c.fmax / amax : 1.0f;
+  c.scale = q8_scale(c.fmax, amax);
   // wave-uniform values: keep them in scalar registers (the LayerNorm backward runs at its 128-register bound)
   c.scale = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c.scale)));
   c.fmax = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c.fmax)));

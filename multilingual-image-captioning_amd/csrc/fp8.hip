@@ -4,7 +4,7 @@
 // weights, e5m2 for gradients, one scale per tensor taken from that tensor's CURRENT absolute maximum.
 //
 //   mic_fp8_amax      state[0] = max |x| over the valid region (atomic max on the float bits; caller zeroes state)
-//   mic_fp8_quantize  scale = FMAX / amax;  q[r][c] = fp8(x[r][c] * scale)  (row-major, k-contiguous for  x W^T  /  dy W)
+//   mic_fp8_quantize  scale = min(FMAX / amax, FLT_MAX);  q[r][c] = fp8(x[r][c] * scale)  (row-major, k-contiguous for  x W^T  /  dy W)
 //                     qT[c][r] = the same bytes transposed, rows zero-padded to rows_pad (k-contiguous for  dy^T x : both
 //                     operands of the weight-gradient GEMM reduce over the row index);  state[1] = amax / FMAX, the
 //                     dequantisation factor the GEMM epilogue multiplies back (mic_gemm_args.a_scale_inv / b_scale_inv).
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void fp8_quantize_kernel(QTable tab) {
   const int tid = threadIdx.x;
   const float fmax = I.fmt == MIC_E4M3 ? 448.0f : 57344.0f;
   const float amax = I.state[0];
-  const float scale = amax > 0.f ? fmax / amax : 1.0f;
+  const float scale = q8_scale(fmax, amax);
   if (local == 0 && tid == 0) I.state[1] = amax > 0.f ? amax / fmax : 1.0f;
   float m = 0.f;
   const int cl = (tid & 7) * 8, c = tc * 64 + cl;

@@ -25,7 +25,7 @@ import util_gemm_ref as GR  # noqa: E402
 PRODUCT_PROFILES = ("profiles/r6_train_kernel_stats_serial.txt", "profiles/r6_train_fp8_kernel_stats_serial.txt",
                     "profiles/r6_generate_kernel_stats.txt")
 COVERAGE_PROFILE = "profiles/attn_conformance_kernel_stats.txt"
-Q8_KERNEL = "attn_bwd_kernel<unsigned short, true>"  # fp8 emission: tests/test_fp8_fused_gpu.py
+Q8_KERNEL = "attn_bwd_kernel<unsigned short, true>"  # fp8 emission: tests/test_fp8_conformance_gpu.py
 OLD_TOL, OLD_TOL_GRAD = 1.2e-2, 3e-2
 
 
@@ -317,7 +317,7 @@ def _instantiations(path):
 def test_coverage_of_the_build_and_the_product_profiles():
     """the GPU module's committed kernel trace launches every attention instantiation the cases claim, every attn_* / kv_append
     kernel of the build's resource table and of the product's committed profiles — all but the fp8-emitting backward, which
-    tests/test_fp8_fused_gpu.py compares with the bf16 kernel checked here"""
+    tests/test_fp8_conformance_gpu.py checks against the fp64 reference used here"""
     ns = lambda names: {re.sub(r"\s+", "", n) for n in names}  # noqa: E731
     traced = _instantiations(COVERAGE_PROFILE)
     claimed = ns(k for c in AC.ALL for dt in AC.DTYPES for k in AC.kernels_of(c["claim"], dt)) | ns(k for dt in AC.DTYPES for k in AC.kernels_of("kv_append", dt))

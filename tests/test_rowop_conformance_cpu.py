@@ -5,7 +5,7 @@
     tests/test_ops_gpu.py (max-scaled relerr under tol(dtype)) is shown to accept the defective result;
   - every kernel instantiation in scope is claimed by a case, launched by the GPU module (its committed kernel listing) and covers
     the build's resource table and the product's committed profiles.
-Out of scope (as in the GPU module): the _q8 forms, embeddings / ViT assembly / colsum, the decode epilogues."""
+Out of scope (as in the GPU module): the _q8 forms (tests/test_fp8_conformance_{cpu,gpu}.py), embeddings / ViT assembly / colsum, the decode epilogues."""
 import json
 import os
 import re
@@ -304,7 +304,7 @@ def _instantiations(path):
 def test_coverage_of_the_build_and_the_product_profiles():
     """the GPU module's committed kernel listing launches every instantiation in scope; the build's resource table and the product's
     committed profiles hold no LayerNorm / CE / AdamW / transpose instantiation beyond those and the fp8-emitting forms, which
-    tests/test_fp8_fused_gpu.py ties bit for bit to the producers checked here"""
+    tests/test_fp8_conformance_gpu.py checks against fp64 and an fp8 reference of its own"""
     ns = lambda names: {re.sub(r"\s+", "", n) for n in names}  # noqa: E731
     traced = _instantiations(COVERAGE_PROFILE)
     assert ns(RC.KERNELS) <= traced, sorted(ns(RC.KERNELS) - traced)

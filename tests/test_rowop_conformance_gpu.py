@@ -9,8 +9,8 @@ the fp64 references and derived per-element bounds of tests/util_rowop_ref.py.  
   - every path without atomics runs twice from the same inputs and gives identical bits (all but dgamma / dbeta of
     mic_layernorm_bwd and the colsum of mic_ce_bwd_t); in-place kernels get their inputs restored between the runs.
 The backward of LayerNorm is checked on the mean / rstd it is handed (the device forward's, as stored) and once end to end.
-Out of scope: the _q8 forms (tests/test_fp8_fused_gpu.py ties them bit for bit to "producer then quantise", so conformance of the
-producers carries over); the decode epilogues are in tests/test_decode_conformance_gpu.py, embeddings, the ViT assembly and colsum in
+Out of scope: the _q8 forms (tests/test_fp8_conformance_gpu.py checks their bf16 outputs against these references and their bytes
+against an fp8 reference of its own); the decode epilogues are in tests/test_decode_conformance_gpu.py, embeddings, the ViT assembly and colsum in
 tests/test_scatter_conformance_gpu.py."""
 import os
 import sys
