@@ -537,6 +537,13 @@ int mic_adamw_clip(int64_t n, float* p, float* m, float* v, const float* g, cons
 int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int ld, int k, int forced_token,
                      int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
                      int32_t* top_idx, void* stream);
+/* The same over a shortlist of the vocabulary (generate(allowed_token_ids=...): the head ran over a gathered copy of the embedding).
+ * token_map[V] int32, ascending: column c of the logits is token token_map[c].  V is the number of columns, forced_token and
+ * eos_token_id are COLUMN numbers (the host finds them in the sorted map); ordering is as above (value desc, column asc = token id
+ * asc, the map being ascending) and every index written to top_idx is token_map[column].  token_map == NULL is mic_row_lse_topk. */
+int mic_row_lse_topk_mapped(int dtype, int R, int V, const void* logits, int ld, int k, int forced_token,
+                            int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
+                            int32_t* top_idx, const int32_t* token_map, void* stream);
 
 /* mic_row_lse_topk's results (no forced token) from the head GEMM's per-granule partials: lse by merging ceil(V / 64) pairs, the
  * top-k by scanning only the 64-column granules whose maximum reaches the k-th largest granule maximum (gen:850-873 without
@@ -544,6 +551,10 @@ int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int ld, int k,
 int mic_row_topk_tiles(int dtype, int R, int V, const void* logits, int ld, const float* rowstat, int stat_ld, int k,
                        int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
                        int32_t* top_idx, void* stream);
+/* ... over a shortlist: token_map as for mic_row_lse_topk_mapped (NULL: mic_row_topk_tiles) */
+int mic_row_topk_tiles_mapped(int dtype, int R, int V, const void* logits, int ld, const float* rowstat, int stat_ld, int k,
+                              int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
+                              int32_t* top_idx, const int32_t* token_map, void* stream);
 
 typedef struct {
   int B, K, max_len, V;

@@ -125,6 +125,7 @@ _SIGS = {
     "mic_ce_rows": ([_i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _p], C.c_int),
     "mic_ce_rows_tiles": ([_i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p], C.c_int),
     "mic_row_topk_tiles": ([_i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p], C.c_int),
+    "mic_row_topk_tiles_mapped": ([_i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p], C.c_int),
     "mic_ce_reduce": ([_i, _p, _p, _p, _p, _p], C.c_int),
     "mic_ce_bwd": ([_i, _i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _f, _p], C.c_int),
     "mic_ce_bwd_t": ([_i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _f, _p, _i, _i, _p, _p], C.c_int),
@@ -151,6 +152,7 @@ _SIGS = {
     "mic_clip_coef": ([_p, _i64, _f, C.c_double, _p, _p], C.c_int),
     "mic_adamw_clip": ([_i64, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _p], C.c_int),
     "mic_row_lse_topk": ([_i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p], C.c_int),
+    "mic_row_lse_topk_mapped": ([_i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p], C.c_int),
     "mic_beam_step": ([C.POINTER(BeamStepArgs), _p], C.c_int),
     "mic_row_forced_topk": ([_i, _i, _p, _p, _p, _p, _p], C.c_int),
     "mic_beam_step_groups": ([C.POINTER(BeamStepArgs), _i, _p], C.c_int),

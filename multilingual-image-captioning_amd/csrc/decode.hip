@@ -17,6 +17,12 @@ __device__ __forceinline__ void forced_entry(int forced, int t, float bias, floa
   val = t == 0 ? 0.f + bias : -INFINITY;
 }
 
+// The index a top-k kernel stores for column c: the column itself, or — the columns being a shortlist of the vocabulary — the token
+// it stands for.  A slot no column filled (a row of NaNs) keeps its out-of-range marker instead of indexing the map with it.
+__device__ __forceinline__ int out_index(const int32_t* __restrict__ token_map, int c, int V) {
+  return token_map && (unsigned)c < (unsigned)V ? token_map[c] : c;
+}
+
 // ------------------------------------------------------------------ per-row lse + top-k
 // One 256-thread block per row of the [R][ld] logits.  Pass 1 streams the row once: online (max, sum-exp) and each
 // thread's own maximum.  The 8th largest of the 256 thread maxima is a provable lower bound tau on the row's k-th best
@@ -28,7 +34,7 @@ template <typename T, int KMAX>
 __global__ __launch_bounds__(256) void row_lse_topk_kernel(int V, const T* __restrict__ logits, int ld, int k, int forced,
                                                            int suppress_eos, int eos, int raw, const float* __restrict__ row_bias,
                                                            float* __restrict__ top_val, int32_t* __restrict__ top_idx,
-                                                           const int32_t* __restrict__ forced_rows) {
+                                                           const int32_t* __restrict__ forced_rows, const int32_t* __restrict__ token_map) {
   __shared__ float sm[256], ss[256];
   __shared__ int si[256];
   const int row = blockIdx.x, tid = threadIdx.x;
@@ -42,7 +48,7 @@ __global__ __launch_bounds__(256) void row_lse_topk_kernel(int V, const T* __res
       float val; int idx;
       forced_entry(forced, tid, bias, val, idx);
       top_val[(size_t)row * k + tid] = val;
-      top_idx[(size_t)row * k + tid] = idx;
+      top_idx[(size_t)row * k + tid] = out_index(token_map, idx, V);
     }
     return;
   }
@@ -111,7 +117,7 @@ __global__ __launch_bounds__(256) void row_lse_topk_kernel(int V, const T* __res
       if (tid < o && better(sm[tid + o], si[tid + o], sm[tid], si[tid])) { sm[tid] = sm[tid + o]; si[tid] = si[tid + o]; }
       __syncthreads();
     }
-    if (tid == 0) { top_val[row] = sm[0] + bias; top_idx[row] = si[0]; }
+    if (tid == 0) { top_val[row] = sm[0] + bias; top_idx[row] = out_index(token_map, si[0], V); }
     return;
   }
   // ---- tau: the KMAX-th largest thread maximum (processed domain): at least KMAX >= k distinct elements are >= tau
@@ -185,7 +191,7 @@ __global__ __launch_bounds__(256) void row_lse_topk_kernel(int V, const T* __res
       __syncthreads();
     }
     const int winner = __float_as_int(ss[0]);
-    if (tid == 0) { top_val[(size_t)row * k + round] = sm[0]; top_idx[(size_t)row * k + round] = si[0]; }
+    if (tid == 0) { top_val[(size_t)row * k + round] = sm[0]; top_idx[(size_t)row * k + round] = out_index(token_map, si[0], V); }
     if (tid == winner) {
 #pragma unroll
       for (int p = 0; p < KMAX - 1; ++p) { bv[p] = bv[p + 1]; bi[p] = bi[p + 1]; }
@@ -194,20 +200,28 @@ __global__ __launch_bounds__(256) void row_lse_topk_kernel(int V, const T* __res
     __syncthreads();
   }
 }
-extern "C" int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int ld, int k, int forced_token,
-                                int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
-                                int32_t* top_idx, void* stream) {
+// token_map (may be null): the logits' columns are a shortlist of the vocabulary — column c is token token_map[c], ascending.  V, forced_token and
+// eos_token_id are column numbers; the order (value desc, column asc) is untouched and every index that leaves is token_map[column].
+extern "C" int mic_row_lse_topk_mapped(int dtype, int R, int V, const void* logits, int ld, int k, int forced_token,
+                                       int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
+                                       int32_t* top_idx, const int32_t* token_map, void* stream) {
   MIC_CHECK(R > 0 && V > 0 && ld >= V && ld % 8 == 0 && k >= 1 && k <= TOPK_WIDE && logits && top_val && top_idx, "mic_row_lse_topk: bad args (k <= 64)");
   // lax.top_k refuses k > V; the unfilled slots would come back as (-inf, 0x7fffffff) and flow into next_token
   MIC_CHECK(k <= V && forced_token < V, "mic_row_lse_topk: k and forced_token must not exceed V");
   dim3 grid(R), block(256);
-#define TOPK_LAUNCH(TT, KM) hipLaunchKernelGGL((row_lse_topk_kernel<TT, KM>), grid, block, 0, (hipStream_t)stream, V, (const TT*)logits, ld, k, forced_token, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx, (const int32_t*)nullptr)
+#define TOPK_LAUNCH(TT, KM) hipLaunchKernelGGL((row_lse_topk_kernel<TT, KM>), grid, block, 0, (hipStream_t)stream, V, (const TT*)logits, ld, k, forced_token, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx, (const int32_t*)nullptr, token_map)
   if (dtype == MIC_BF16) { if (k <= 8) TOPK_LAUNCH(uint16_t, 8); else if (k <= 16) TOPK_LAUNCH(uint16_t, 16); else if (k <= 32) TOPK_LAUNCH(uint16_t, 32); else TOPK_LAUNCH(uint16_t, 64); }
   else if (dtype == MIC_F32) { if (k <= 8) TOPK_LAUNCH(float, 8); else if (k <= 16) TOPK_LAUNCH(float, 16); else if (k <= 32) TOPK_LAUNCH(float, 32); else TOPK_LAUNCH(float, 64); }
   else MIC_CHECK(false, "mic_row_lse_topk: bad dtype");
 #undef TOPK_LAUNCH
   MIC_LAUNCH_CHECK();
   return MIC_OK;
+}
+extern "C" int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int ld, int k, int forced_token,
+                                int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
+                                int32_t* top_idx, void* stream) {
+  return mic_row_lse_topk_mapped(dtype, R, V, logits, ld, k, forced_token, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx,
+                                 nullptr, stream);
 }
 
 // The forced branch of row_lse_topk_kernel with the token read per row (gen:412-419 when the rows of one launch belong to calls with
@@ -216,7 +230,7 @@ extern "C" int mic_row_forced_topk(int R, int k, const int32_t* forced_rows, con
                                    void* stream) {
   MIC_CHECK(R > 0 && k >= 1 && k <= TOPK_WIDE && forced_rows && top_val && top_idx, "mic_row_forced_topk: bad args (k <= 64)");
   hipLaunchKernelGGL((row_lse_topk_kernel<float, TOPK_WIDE>), dim3(R), dim3(256), 0, (hipStream_t)stream, 0, (const float*)nullptr, 0, k, -1, 0, 0, 0,
-                     row_bias, top_val, top_idx, forced_rows);
+                     row_bias, top_val, top_idx, forced_rows, (const int32_t*)nullptr);
   MIC_LAUNCH_CHECK();
   return MIC_OK;
 }
@@ -252,7 +266,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void row_topk_tiles_kernel(int V, const T* __restrict__ logits, int ld, const float2* __restrict__ stat,
                                                             int stat_ld, int ntiles, int k, int suppress_eos, int eos, int raw,
                                                             const float* __restrict__ row_bias, float* __restrict__ top_val,
-                                                            int32_t* __restrict__ top_idx) {
+                                                            int32_t* __restrict__ top_idx, const int32_t* __restrict__ token_map) {
   constexpr int TPT = 16;                     // granules per thread: up to 4096 granules of 64 columns (V <= 262 144)
   constexpr int NCAND = 2 * (TOPK_MAX + 1);   // >= 2 kk - 1 candidate granules
   constexpr int CPT = (NCAND + 3) / 4;        // candidate granules per wave
@@ -400,24 +414,31 @@ __global__ __launch_bounds__(256) void row_topk_tiles_kernel(int V, const T* __r
     }
     block_best(bv, bi);
     pv = bv; pidx = bi;
-    if (tid == 0) { top_val[(size_t)row * k + round] = pv; top_idx[(size_t)row * k + round] = pidx; }
+    if (tid == 0) { top_val[(size_t)row * k + round] = pv; top_idx[(size_t)row * k + round] = out_index(token_map, pidx, V); }
   }
 }
-extern "C" int mic_row_topk_tiles(int dtype, int R, int V, const void* logits, int ld, const float* rowstat, int stat_ld, int k,
-                                  int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
-                                  int32_t* top_idx, void* stream) {
+// token_map: as for mic_row_lse_topk_mapped (null: the indices leave as they are)
+extern "C" int mic_row_topk_tiles_mapped(int dtype, int R, int V, const void* logits, int ld, const float* rowstat, int stat_ld, int k,
+                                         int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
+                                         int32_t* top_idx, const int32_t* token_map, void* stream) {
   const int ntiles = (V + 63) / 64;
   MIC_CHECK(R > 0 && V > 0 && ld >= V && k >= 1 && k <= TOPK_MAX && logits && rowstat && top_val && top_idx && stat_ld >= ntiles && ntiles <= 4096,
             "mic_row_topk_tiles: bad args (V <= 262144)");
   MIC_CHECK(k <= V, "mic_row_topk_tiles: k must not exceed V");
   dim3 grid(R), block(256);
   if (dtype == MIC_BF16)
-    hipLaunchKernelGGL(row_topk_tiles_kernel<uint16_t>, grid, block, 0, (hipStream_t)stream, V, (const uint16_t*)logits, ld, (const float2*)rowstat, stat_ld, ntiles, k, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx);
+    hipLaunchKernelGGL(row_topk_tiles_kernel<uint16_t>, grid, block, 0, (hipStream_t)stream, V, (const uint16_t*)logits, ld, (const float2*)rowstat, stat_ld, ntiles, k, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx, token_map);
   else if (dtype == MIC_F32)
-    hipLaunchKernelGGL(row_topk_tiles_kernel<float>, grid, block, 0, (hipStream_t)stream, V, (const float*)logits, ld, (const float2*)rowstat, stat_ld, ntiles, k, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx);
+    hipLaunchKernelGGL(row_topk_tiles_kernel<float>, grid, block, 0, (hipStream_t)stream, V, (const float*)logits, ld, (const float2*)rowstat, stat_ld, ntiles, k, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx, token_map);
   else MIC_CHECK(false, "mic_row_topk_tiles: bad dtype");
   MIC_LAUNCH_CHECK();
   return MIC_OK;
+}
+extern "C" int mic_row_topk_tiles(int dtype, int R, int V, const void* logits, int ld, const float* rowstat, int stat_ld, int k,
+                                  int suppress_eos, int eos_token_id, int raw_logits, const float* row_bias, float* top_val,
+                                  int32_t* top_idx, void* stream) {
+  return mic_row_topk_tiles_mapped(dtype, R, V, logits, ld, rowstat, stat_ld, k, suppress_eos, eos_token_id, raw_logits, row_bias, top_val, top_idx,
+                                   nullptr, stream);
 }
 
 // ------------------------------------------------------------------ one beam_search_body_fn iteration (gen:857-966)

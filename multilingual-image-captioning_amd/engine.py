@@ -40,6 +40,42 @@ def packed_attn_tiled(Tq_max: int, Tk: int) -> bool:
     return Tq_max > 64 or Tk > 64
 
 
+class Shortlist:
+    """A vocabulary shortlist for the LM head (generate(allowed_token_ids=...)): the Ns sorted unique token ids `map`, the rows
+    `E` [Ns_pad][d] of the tied embedding they name (compute dtype) and their entries `bias` [Ns_pad] of final_logits_bias (fp32);
+    Ns_pad = Ns rounded up to 128, the padding rows and entries zero.  The tensors are allocated once and stay where they are — captured
+    decoder steps hold their addresses — and `refresh()` re-gathers them in place when the weights have moved (ParamStore.version: the
+    rule Engine.ln_folded follows)."""
+
+    def __init__(self, engine: "Engine", ids, key):
+        P = engine.P
+        self.engine, self.key = engine, key            # key = (Ns, digest of the ids): the identity decode plans are keyed by
+        self.ids = ids                                 # numpy int32, sorted unique (host copy: token -> column lookups)
+        self.Ns, self.Ns_pad = int(ids.size), _rup(int(ids.size), ROWPAD)
+        self.map = torch.from_numpy(ids).to(P.device)
+        self._rows = self.map.long()                   # (index_select wants int64)
+        self.E = torch.zeros((self.Ns_pad, P.d), dtype=P.dtype, device=P.device)
+        self.bias = torch.zeros(self.Ns_pad, dtype=torch.float32, device=P.device)
+        self.version = None
+
+    def column(self, token: int) -> int:
+        """the column of vocabulary id `token` (which must be on the list)"""
+        import numpy as np
+
+        i = int(np.searchsorted(self.ids, token))
+        if i >= self.Ns or int(self.ids[i]) != int(token):
+            raise ValueError(f"token {token} is not in the vocabulary shortlist")
+        return i
+
+    def refresh(self):
+        P = self.engine.P
+        ver = getattr(P, "version", 0)
+        if ver != self.version:
+            ops.copy_rows(P.w("shared"), self.E, self.Ns, P.d, src_idx=self.map)
+            torch.index_select(P.f32("flb"), 0, self._rows, out=self.bias[: self.Ns])
+            self.version = ver
+
+
 class Engine(Fp8Views):
     def __init__(self, store: ParamStore):
         self.P = store
@@ -650,11 +686,21 @@ class Engine(Fp8Views):
             ops.gemm(ehs, w, kvcat, Mv, P.L * 2 * P.d, P.d, bias=b)
         return kvcat
 
-    def head_logits(self, hf, M: int, name: str = "d.logits", stats: bool = False, fp8: bool = False):
+    def head_logits(self, hf, M: int, name: str = "d.logits", stats: bool = False, fp8: bool = False, shortlist: Optional[Shortlist] = None):
         """Tied head (modeling:170-178): logits[M, Vpad] = hf @ shared^T + final_logits_bias (compute dtype).
         stats=True (bf16 mode): also returns the GEMM's softmax partials per 64-column granule [M][Vpad/64][2] (fp32) so that the
-        log-softmax downstream (cross-entropy, beam scores) needs no second pass over the logits."""
+        log-softmax downstream (cross-entropy, beam scores) needs no second pass over the logits.
+        shortlist (up to date: Shortlist.refresh): the same GEMM over the shortlist's gathered rows only — logits [M, Ns_pad], column c =
+        token shortlist.map[c], partials over the Ns valid columns — into buffers of their own (the full-vocabulary ones are untouched)."""
         P = self.P
+        if shortlist is not None:
+            sl = shortlist
+            logits = self.buf(name + ".sl", M, sl.Ns_pad)
+            stat = None
+            if stats and self.dt == torch.bfloat16 and self.use_head_stats:
+                stat = self.buf(name + ".sl.stat", M, 2 * (sl.Ns_pad // 64), torch.float32)
+            ops.gemm(hf, sl.E, logits, M, sl.Ns_pad, P.d, bias=sl.bias, rowstat=stat, rowstat_nvalid=sl.Ns)
+            return (logits, stat) if stats else logits
         logits = self.buf(name, M, P.Vpad)
         stat = self.head_stats(name, M) if stats else None
         self._head_project(hf, logits, M, stat, fp8=fp8)  # (fp8: the train / eval passes only — inference stays in the storage dtype)

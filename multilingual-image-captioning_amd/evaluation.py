@@ -97,18 +97,36 @@ def evaluate(trainer, eval_loaders: Dict[str, Iterable[dict]], lang_code_to_id: 
     return out
 
 
+def vocabulary_shortlist(id_arrays, always=()) -> np.ndarray:
+    """The sorted unique int32 token ids that occur in an iterable of label arrays (any shape, e.g. the `input_ids` of the
+    training captions), plus `always` (EOS, the language ids ...): the `allowed_token_ids` of `generate` / `generate_languages`
+    for a model that only ever has to write what its captions contain."""
+    parts = [np.asarray(list(always), dtype=np.int64).reshape(-1)]
+    for a in id_arrays:
+        a = np.asarray(a.cpu() if hasattr(a, "cpu") else a)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"vocabulary_shortlist: token ids must be integers, got dtype {a.dtype}")
+        parts.append(a.reshape(-1).astype(np.int64))
+    ids = np.unique(np.concatenate(parts))
+    if ids.size and (ids[0] < 0 or ids[-1] > np.iinfo(np.int32).max):
+        raise ValueError(f"vocabulary_shortlist: token ids out of range: min {int(ids[0])}, max {int(ids[-1])}")
+    return ids.astype(np.int32)
+
+
 def generate_languages(model, pixel_values, lang_ids: Dict[str, int], *, via: str = "forced_bos", max_length: int = 64,
-                       num_beams: int = 4) -> Dict[str, np.ndarray]:
+                       num_beams: int = 4, allowed_token_ids=None) -> Dict[str, np.ndarray]:
     """Captions of the same images in every language of `lang_ids` ({"en_XX": id, ...}) from ONE `generate` call: the language
     ids go in as a sequence, the images are encoded once and all languages share one decode chain; the result per language is
     that of its own call (`evaluation.py:80-94` calls generate once per language).  `via` names the argument that selects the
     language: "forced_bos" (`forced_bos_token_id`) or "decoder_start" (`decoder_start_token_id`, main.py:820).
+    `allowed_token_ids`: the vocabulary shortlist of `generate`, shared by all languages (see `vocabulary_shortlist`).
     Returns {language: int32 ids [batch, max_length]}.  `evaluate()` keeps one call per language: its loaders carry different
     images per language."""
     arg = {"forced_bos": "forced_bos_token_id", "decoder_start": "decoder_start_token_id"}.get(via)
     if arg is None:
         raise ValueError(f"via={via!r}: expected 'forced_bos' or 'decoder_start'")
     langs = list(lang_ids)
-    gen = model.generate(pixel_values, max_length=max_length, num_beams=num_beams, **{arg: [int(lang_ids[l]) for l in langs]})
+    gen = model.generate(pixel_values, max_length=max_length, num_beams=num_beams, allowed_token_ids=allowed_token_ids,
+                         **{arg: [int(lang_ids[l]) for l in langs]})
     seq = np.asarray(gen.sequences.cpu())
     return {l: seq[g] for g, l in enumerate(langs)}

@@ -25,6 +25,12 @@ back-to-back launches cost: the ~10 us per dependent kernel are the kernels' own
 reduction and epilogue), not launch overhead, so the graphs are correct (tests) but buy nothing for a single chain and stay
 opt-in there; fewer, fatter kernels per step are what would move small-batch latency.  A beam search cut into image slices
 (MIC_DECODE_SLICES) uses the graphs to run the slices' chains as parallel branches.
+
+Vocabulary shortlist (`generate(allowed_token_ids=A)`): the head GEMM runs over the len(A) gathered rows of the tied embedding
+(`engine.Shortlist`), the top-k kernels over those columns with a token map (`mic_row_lse_topk_mapped`, `mic_row_topk_tiles_mapped`):
+the candidates leave as vocabulary ids, so `mic_beam_step` / `mic_greedy_step` and the embedding lookup of the next step see no
+difference, and the step has the same number of launches.  A decode plan is keyed by the shortlist's identity and keeps the object
+alive: captured steps hold its tensors' addresses, the column count and the EOS column.
 """
 from __future__ import annotations
 
@@ -37,6 +43,7 @@ from . import ops
 NEG = -1.0e7
 _POLL = 8          # decoder steps between two looks at the device-side stop flag
 _MAX_PLANS = 2     # decode plans kept per model (each owns a KV cache: 24 x rows x max_length x d_model elements)
+_MAX_SHORTLISTS = 4  # vocabulary shortlists kept per model (each owns len(A) gathered embedding rows)
 _AUTO_SLICES = 1   # MIC_DECODE_SLICES=auto
 
 
@@ -102,10 +109,60 @@ def normalize_language_ids(decoder_start_token_id=None, forced_bos_token_id=None
     return G, out[0], out[1], True
 
 
+def normalize_allowed_token_ids(allowed_token_ids, vocab_size: int, *, eos_token_id=None, forced_bos_token_id=None,
+                                forced_eos_token_id=None, language_bos_ids=None, num_beams: int = 1, do_sample: bool = False):
+    """`generate(allowed_token_ids=A)` -> A as a sorted, duplicate-free int32 numpy array (sorted: the head's compact column order is
+    then vocabulary order, so top-k ties break by ascending token id exactly as over the whole vocabulary).
+
+    A is a 1-D integer sequence (list, tuple, numpy or torch).  ValueError for an empty, non-integer or non-1-D A, ids outside
+    [0, vocab_size), and for anything the search must be able to emit but could not: `eos_token_id`, the scalar `forced_bos_token_id` /
+    `forced_eos_token_id` in force for the call, every entry of `language_bos_ids` (the per-language BOS ids of a grouped call) — pass
+    None for what is not in force — and len(A) < 2 * num_beams for a beam search (top-k refuses k > columns).  Start ids are inputs and
+    PAD is written by the bookkeeping: neither has to be in A.  Sampling draws noise per vocabulary column: NotImplementedError."""
+    import numpy as np
+
+    a = allowed_token_ids
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    if isinstance(a, (list, tuple)):
+        for v in a:
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"`allowed_token_ids`: token ids must be integers, got {v!r}")
+        a = np.asarray(a, dtype=np.int64)
+    if not isinstance(a, np.ndarray):
+        raise ValueError(f"`allowed_token_ids`: expected a 1-D sequence of integers, got {type(allowed_token_ids).__name__}")
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"`allowed_token_ids` must be a 1-D integer array, got shape {a.shape} dtype {a.dtype}")
+    if a.size == 0:
+        raise ValueError("`allowed_token_ids` is empty")
+    if int(a.min()) < 0 or int(a.max()) >= vocab_size:
+        raise ValueError(f"`allowed_token_ids` holds ids outside the vocabulary [0, {vocab_size}): min {int(a.min())}, max {int(a.max())}")
+    ids = np.unique(a).astype(np.int32)  # sorted
+    if do_sample:
+        raise NotImplementedError("do_sample=True with `allowed_token_ids` is not implemented: the sampling noise is indexed by vocabulary "
+                                  "column; a shortlist serves greedy and beam search only")
+
+    def member(v) -> bool:
+        i = int(np.searchsorted(ids, v))
+        return i < ids.size and int(ids[i]) == int(v)
+
+    for name, v in (("eos_token_id", eos_token_id), ("forced_bos_token_id", forced_bos_token_id), ("forced_eos_token_id", forced_eos_token_id)):
+        if v is not None and not member(v):
+            raise ValueError(f"`{name}`={int(v)} is not in `allowed_token_ids`: the search has to be able to emit it")
+    for v in language_bos_ids or ():
+        if not member(v):
+            raise ValueError(f"the language id {int(v)} (`forced_bos_token_id`) is not in `allowed_token_ids`")
+    if num_beams > 1 and ids.size < 2 * num_beams:
+        raise ValueError(f"`allowed_token_ids` has {ids.size} distinct ids: beam search with num_beams={num_beams} ranks 2 * num_beams = "
+                         f"{2 * num_beams} candidates per row")
+    return ids
+
+
 class _DecodePlan:
     """Fixed-address device state of one generate configuration + its captured decoder steps."""
 
     def __init__(self):
+        self.shortlist = None  # generate(allowed_token_ids=...): the engine.Shortlist whose tensors the captured steps point into
         self.t = {}          # name -> persistent tensor
         self.graphs = {}     # cur_len -> torch.cuda.CUDAGraph
         self.calls = 0
@@ -182,7 +239,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
                  num_beams: Optional[int] = None, no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None,
                  forced_bos_token_id: Optional[int] = None, forced_eos_token_id: Optional[int] = None,
                  length_penalty: Optional[float] = None, early_stopping: Optional[bool] = None, trace: bool = True,
-                 params=None, **model_kwargs):
+                 params=None, allowed_token_ids=None, **model_kwargs):
         """`FlaxCLIPVisionGenerationMixin.generate` (gen:128-336): same arguments, defaults from `config.mbart_config`, same dispatch —
         greedy (`num_beams == 1`, no sampling), sampling (`do_sample`, one beam) or beam search; `input_ids` = pixel values.
         Limits of this build (the reference has none of the first two; the third is the reference's own): `num_beams <= 32` — the fused
@@ -197,7 +254,16 @@ class FlaxCLIPVisionMBartGenerationMixin:
         once, cross-attention K/V are projected once per image, decoder row = (image * G + g) * num_beams + beam.  Returns
         `sequences [G, B, max_length]` and, for beam search, `scores [G, B]` and `out["steps"]` = a list of G step counts.  Greedy and
         beam search only (`do_sample=True` raises NotImplementedError); the search runs unsliced (MIC_DECODE_SLICES is ignored here);
-        MIC_DECODE_GRAPHS=1 works as for a single chain."""
+        MIC_DECODE_GRAPHS=1 works as for a single chain.
+
+        Vocabulary shortlist: `allowed_token_ids=A` (a 1-D integer sequence: list, tuple, numpy or torch; order and duplicates do not matter)
+        returns what the same call returns on a model whose `final_logits_bias` is -inf outside A and unchanged inside: log-softmax
+        normalised over A, top-k ties to the lower vocabulary id, `scores` accordingly, the processors and stop tests as they are.  The
+        LM head then runs over len(A) gathered rows of the tied embedding instead of the whole vocabulary (gathered once per distinct A and
+        kept on the model; refreshed in place when the weights move).  `eos_token_id`, a scalar forced BOS / EOS id in force, every
+        per-language BOS id and, for beam search, len(A) >= 2 * num_beams are required of A (ValueError, before any device work); start ids
+        and PAD need not be in it.  One set per call (the languages of a grouped call share it); `do_sample=True` raises
+        NotImplementedError.  None (default): the whole vocabulary."""
         mc = self.config.mbart_config
         G, bos_ids, start_ids, grouped = normalize_language_ids(decoder_start_token_id, forced_bos_token_id)
         if grouped:  # resolved per language below; the scalar code in between sees "not given"
@@ -228,10 +294,18 @@ class FlaxCLIPVisionMBartGenerationMixin:
             for ids in (lang["start"], lang["bos"] or []):  # these index the embedding table on the device
                 if any(not 0 <= v < mc.vocab_size for v in ids):
                     raise ValueError(f"language ids {ids} outside the vocabulary [0, {mc.vocab_size})")
+        allowed = None
+        if allowed_token_ids is not None:  # host-only checks, before the encoder runs
+            allowed = normalize_allowed_token_ids(
+                allowed_token_ids, mc.vocab_size, eos_token_id=eos_token_id,
+                forced_bos_token_id=None if lang else (forced_bos_token_id if forced_bos_token_id is not None else mc.forced_bos_token_id),
+                forced_eos_token_id=forced_eos_token_id if forced_eos_token_id is not None else mc.forced_eos_token_id,
+                language_bos_ids=lang["bos"] if lang else None, num_beams=num_beams, do_sample=bool(do_sample))
         # gen:109-120: `params=` is NOT forwarded to encode (the encoder always uses self.params); the decoder uses it.
         enc = self.encode(input_ids, return_dict=True, **{k: v for k, v in model_kwargs.items()
                                                           if not (k.startswith("decoder_") or k.startswith("cross_attn"))})
         self._use_params(params)
+        sl = self._shortlist(allowed) if allowed is not None else None
         ehs = enc["last_hidden_state"]
         B = ehs.shape[0]
         # processors (gen:368-420); `no_repeat_ngram_size` is accepted and ignored like in the reference
@@ -241,7 +315,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
         procs = dict(min_length=min_length if (min_length is not None and eos_token_id is not None and min_length > -1) else None,
                      forced_bos=None if lang else forced_bos_token_id, forced_eos=forced_eos_token_id)  # (per-row BOS ids travel in `lang`)
         if not do_sample and num_beams == 1:
-            return self._greedy_search(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, procs, lang)
+            return self._greedy_search(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, procs, lang, sl)
         elif do_sample and num_beams == 1:
             mcfg = mc
             top_k = top_k if top_k is not None else getattr(mcfg, "top_k", 50)  # gen:349-356
@@ -254,7 +328,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
             length_penalty = length_penalty if length_penalty is not None else mc.length_penalty  # gen:733-742
             early_stopping = early_stopping if early_stopping is not None else mc.early_stopping
             return self._beam_search(ehs, B, num_beams, decoder_start_token_id, max_length, pad_token_id, eos_token_id,
-                                     length_penalty, early_stopping, procs, lang)
+                                     length_penalty, early_stopping, procs, lang, sl)
         else:
             raise NotImplementedError("`Beam sampling is currently not implemented.")  # gen:336
 
@@ -289,6 +363,39 @@ class FlaxCLIPVisionMBartGenerationMixin:
         """drop the cached decode plans (their KV caches and captured graphs)"""
         self.__dict__.pop("_decode_plans", None)
 
+    def _shortlist(self, ids):
+        """the engine.Shortlist of the sorted unique ids `ids` (normalize_allowed_token_ids): built once per distinct set, a small LRU on
+        the model keyed by a digest of the ids.  A decode plan keeps the one it was built with (`_shortlist_of`)."""
+        import hashlib
+        from collections import OrderedDict
+
+        from .engine import Shortlist
+
+        key = (int(ids.size), hashlib.sha1(ids.tobytes()).hexdigest())
+        cache = self.__dict__.setdefault("_shortlists", OrderedDict())
+        sl = cache.get(key)
+        if sl is None:
+            for plan in self.__dict__.get("_decode_plans", {}).values():  # dropped from the LRU, but a plan's captured steps still point into it
+                if plan.shortlist is not None and plan.shortlist.key == key:
+                    sl = plan.shortlist
+            if sl is None:
+                sl = Shortlist(self.engine, ids, key)
+            while len(cache) >= _MAX_SHORTLISTS:
+                cache.popitem(last=False)
+            cache[key] = sl
+        cache.move_to_end(key)
+        return sl
+
+    def _shortlist_of(self, plan: _DecodePlan, eos_token_id):
+        """(shortlist, columns, EOS column, token map) of a plan — (None, V, eos_token_id, None) for the whole vocabulary.  The plan's own
+        shortlist object is the one its captured steps point into; its gathered rows are brought up to date with the weights here, in
+        place, on the stream the steps follow on."""
+        sl = plan.shortlist
+        if sl is None:
+            return None, self.store.V, eos_token_id, None
+        sl.refresh()
+        return sl, sl.Ns, (sl.column(eos_token_id) if eos_token_id is not None else eos_token_id), sl.map
+
     def _plan_cache(self, plan: _DecodePlan, rows: int, max_length: int) -> dict:
         """the plan's self-attention cache (modeling:249-282: static length max_length).  Not re-zeroed between calls: a step
         only reads the slots <= its own index, all written earlier in the same call."""
@@ -307,8 +414,9 @@ class FlaxCLIPVisionMBartGenerationMixin:
         t[name].view(images, G, beams).copy_(torch.tensor(ids, dtype=torch.int32).to(self.device).view(1, G, 1).expand(images, G, beams))
         return t[name]
 
-    def _greedy_search(self, ehs, B, start_token, max_length, pad_token_id, eos_token_id, procs, lang=None):
-        """lang = None: B rows.  lang = dict(G, start, bos): G searches per image, row = image * G + g (n_img images below)"""
+    def _greedy_search(self, ehs, B, start_token, max_length, pad_token_id, eos_token_id, procs, lang=None, sl=None):
+        """lang = None: B rows.  lang = dict(G, start, bos): G searches per image, row = image * G + g (n_img images below).
+        sl: the engine.Shortlist of generate(allowed_token_ids=...) or None"""
         from .modeling_clip_vision_mbart import ModelOutput
 
         dev, st = self.device, self.store
@@ -326,9 +434,11 @@ class FlaxCLIPVisionMBartGenerationMixin:
             if lang:
                 t["start_rows"] = torch.empty(B, dtype=torch.int32, device=dev)
                 t["bos_rows"] = torch.empty(B, dtype=torch.int32, device=dev)
+            plan.shortlist = sl
 
         plan = self._decode_plan(("greedy", B, max_length, pad_token_id, eos_token_id, procs["min_length"], procs["forced_eos"], self.dtype)
-                                 + ((("G", G),) if lang else ()), build)
+                                 + ((("G", G),) if lang else ()) + ((("A",) + sl.key,) if sl else ()), build)
+        sl, cols, eos_col, tmap = self._shortlist_of(plan, eos_token_id)
         t = plan.t
         sequences, finished, next_token, top_val, top_idx, pos_all = (t[k] for k in ("sequences", "finished", "next_token", "top_val",
                                                                                      "top_idx", "pos_all"))
@@ -351,13 +461,15 @@ class FlaxCLIPVisionMBartGenerationMixin:
             def fn():
                 with ops.pinned_stream():
                     cache["cache_index"] = cur_len - 1
-                    logits = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * B: cur_len * B])
+                    logits = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * B: cur_len * B], shortlist=sl)
                     forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
+                    if sl and forced >= 0:
+                        forced = sl.column(forced)
                     if bos_rows is not None and cur_len == 1 and forced < 0:  # ForcedBOS per language (a ForcedEOS at max_length == 2 wins)
                         ops.row_forced_topk(B, 1, bos_rows, top_val, top_idx)
                     else:
-                        ops.row_lse_topk(logits, logits.stride(0), st.V, 1, top_val, top_idx, B, forced_token=forced, suppress_eos=suppress,
-                                         eos_token_id=eos_token_id, raw_logits=True)
+                        ops.row_lse_topk(logits, logits.stride(0), cols, 1, top_val, top_idx, B, forced_token=forced, suppress_eos=suppress,
+                                         eos_token_id=eos_col, raw_logits=True, token_map=tmap)
                     ops.greedy_step(B, max_length, cur_len, eos_token_id, pad_token_id, top_idx, 1, sequences, finished, next_token)
             return fn
 
@@ -437,7 +549,8 @@ class FlaxCLIPVisionMBartGenerationMixin:
             n -= 1
         return max(n, 1)
 
-    def _beam_search(self, ehs, B, K, start_token, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, lang=None):
+    def _beam_search(self, ehs, B, K, start_token, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, lang=None,
+                     sl=None):
         """lang = None: one search over B images.  lang = dict(G, start, bos): G searches over the same n_img images in one unsliced
         chain — bookkeeping item i = image * G + g belongs to search g (mic_beam_step_groups), its K rows share the image's cross K/V
         with the rows of the other searches (row_div = G * K)."""
@@ -477,9 +590,12 @@ class FlaxCLIPVisionMBartGenerationMixin:
             for sub in plan.subs:
                 build_slice(sub)
             plan.streams = [torch.cuda.Stream(device=dev) for _ in range(NS)] if NS > 1 else []
+            plan.shortlist = sl
 
         plan = self._decode_plan(("beam", B, K, NS, max_length, pad_token_id, eos_token_id, float(length_penalty), bool(early_stopping),
-                                  procs["min_length"], procs["forced_eos"], self.dtype) + ((("G", G),) if lang else ()), build)
+                                  procs["min_length"], procs["forced_eos"], self.dtype) + ((("G", G),) if lang else ())
+                                 + ((("A",) + sl.key,) if sl else ()), build)
+        sl = self._shortlist_of(plan, eos_token_id)[0]
         ehs = ehs.reshape(n_img, st.S * st.d)
         steps_fn = []
         for i, sub in enumerate(plan.subs):
@@ -514,7 +630,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
             # plan is warm) without waiting and looks at the flag only every _POLL steps.
             t["gstate"].zero_()
             steps_fn.append(self._beam_step_fn(cache, t, Bs, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs,
-                                               groups=G if lang else None, bos_rows=bos_rows))
+                                               groups=G if lang else None, bos_rows=bos_rows, sl=sl))
         use_graphs = _graphs_enabled(dev, NS)
 
         def step(cur_len):
@@ -576,10 +692,12 @@ class FlaxCLIPVisionMBartGenerationMixin:
         return out
 
     def _beam_step_fn(self, cache, t, B, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, groups=None,
-                      bos_rows=None):
+                      bos_rows=None, sl=None):
         """the launches of one beam-search step (gen:822-966) of one slice of B items: step(cur_len).  groups = G: the items belong to G
-        searches (item i to search i % G, gstate [G][8]); bos_rows: per-row ForcedBOS ids of such a call"""
+        searches (item i to search i % G, gstate [G][8]); bos_rows: per-row ForcedBOS ids of such a call; sl: the call's vocabulary
+        shortlist (the head and the top-k run over its columns, the candidates leave as vocabulary ids: mic_beam_step sees no difference)"""
         st = self.store
+        cols, eos_col, tmap = (sl.Ns, sl.column(eos_token_id), sl.map) if sl else (st.V, eos_token_id, None)
         R = B * K
         running_seq, seq, finished, running_scores, scores = t["running_seq"], t["seq"], t["finished"], t["running_scores"], t["scores"]
         next_token, src_row, flags, cand_val, cand_idx, pos_all, gstate = (t[k] for k in ("next_token", "src_row", "flags", "cand_val",
@@ -588,18 +706,20 @@ class FlaxCLIPVisionMBartGenerationMixin:
         def step(cur_len):
             with ops.pinned_stream():
                 cache["cache_index"] = cur_len - 1
-                logits, stat = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R], stats=True)  # gen:830-840
+                logits, stat = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R], stats=True, shortlist=sl)  # gen:830-840
                 forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
+                if sl and forced >= 0:
+                    forced = sl.column(forced)
                 if bos_rows is not None and cur_len == 1 and forced < 0:  # ForcedBOS per language (a ForcedEOS at max_length == 2 wins)
                     ops.row_forced_topk(R, 2 * K, bos_rows, cand_val, cand_idx, row_bias=running_scores.reshape(-1))
                 elif stat is not None and forced < 0 and 2 * K <= 16:
                     # log-softmax + top-2K from the head GEMM's per-granule partials: 3908 pairs and a few 64-column granules
                     # per row instead of two passes over the 250 054 logits (same candidates, same order, same fp32 arithmetic)
-                    ops.row_topk_tiles(logits, logits.stride(0), st.V, stat, 2 * K, cand_val, cand_idx, R, suppress_eos=suppress,
-                                       eos_token_id=eos_token_id, row_bias=running_scores.reshape(-1))
+                    ops.row_topk_tiles(logits, logits.stride(0), cols, stat, 2 * K, cand_val, cand_idx, R, suppress_eos=suppress,
+                                       eos_token_id=eos_col, row_bias=running_scores.reshape(-1), token_map=tmap)
                 else:
-                    ops.row_lse_topk(logits, logits.stride(0), st.V, 2 * K, cand_val, cand_idx, R, forced_token=forced,
-                                     suppress_eos=suppress, eos_token_id=eos_token_id, row_bias=running_scores.reshape(-1))  # gen:850-873
+                    ops.row_lse_topk(logits, logits.stride(0), cols, 2 * K, cand_val, cand_idx, R, forced_token=forced,
+                                     suppress_eos=suppress, eos_token_id=eos_col, row_bias=running_scores.reshape(-1), token_map=tmap)  # gen:850-873
                 ops.beam_step(B, K, max_length, st.V, cur_len, eos_token_id, pad_token_id, length_penalty, early_stopping, cand_val,
                               cand_idx, running_seq, running_scores, seq, scores, finished, src_row, next_token, flags, gstate=gstate,
                               groups=groups)  # gen:872-966

@@ -365,8 +365,9 @@ class FlaxCLIPVisionMBartForConditionalGeneration(FlaxCLIPVisionMBartPreTrainedM
                     if l > 0 or not wn.endswith("qkv"):
                         eng.ln_folded(wn, ln)
 
-    def _decode_step(self, cache: dict, tokens: torch.Tensor, pos: torch.Tensor, stats: bool = False):
-        """stats=True: returns (logits, per-tile softmax partials of the head GEMM or None in float32 mode)
+    def _decode_step(self, cache: dict, tokens: torch.Tensor, pos: torch.Tensor, stats: bool = False, shortlist=None):
+        """stats=True: returns (logits, per-tile softmax partials of the head GEMM or None in float32 mode).  shortlist (an
+        engine.Shortlist, generate(allowed_token_ids=...) only): the head runs over its columns (Engine.head_logits)
 
         bfloat16 mode folds the decoder layer's LayerNorms around the GEMMs (engine.ln_folded / mic_gemm_args.a_ln_stats): the
         GEMM that writes a residual-stream tensor (self-attention out, cross-attention out, fc2) also accumulates (sum, sum of
@@ -433,7 +434,7 @@ class FlaxCLIPVisionMBartForConditionalGeneration(FlaxCLIPVisionMBartPreTrainedM
         hf = eng.buf(ns + "g.hf", R, d)
         ops.layernorm_fwd(x, P.f32("dec.ln_f.g"), P.f32("dec.ln_f.b"), eng.dec_eps, hf, rows=R)
         cache["cache_index"] = cur + 1
-        return eng.head_logits(hf, R, name=ns + "g.logits", stats=stats)
+        return eng.head_logits(hf, R, name=ns + "g.logits", stats=stats, shortlist=shortlist)
 
     # ------------------------------------------------------------------ construction (modeling:703-773)
     @classmethod

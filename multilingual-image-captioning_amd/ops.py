@@ -354,7 +354,14 @@ def ce_rows_tiles(logits, ld, V, rowstat, labels, row_lse, row_loss, rows):
                                       _p(row_loss), _stream()), "mic_ce_rows_tiles")
 
 
-def row_topk_tiles(logits, ld, V, rowstat, k, top_val, top_idx, R, *, suppress_eos=False, eos_token_id=2, raw_logits=False, row_bias=None):
+def row_topk_tiles(logits, ld, V, rowstat, k, top_val, top_idx, R, *, suppress_eos=False, eos_token_id=2, raw_logits=False, row_bias=None,
+                   token_map=None):
+    """token_map (int32 [V], ascending): the columns are a vocabulary shortlist — V and eos_token_id count columns, top_idx gets token_map[column]"""
+    if token_map is not None:
+        L.check(L.lib().mic_row_topk_tiles_mapped(_dt(logits), R, V, _p(logits), ld, _p(rowstat), rowstat.stride(0) // 2, k, int(suppress_eos),
+                                                  eos_token_id, int(raw_logits), _p(row_bias), _p(top_val), _p(top_idx), _p(token_map), _stream()),
+                "mic_row_topk_tiles_mapped")
+        return
     L.check(L.lib().mic_row_topk_tiles(_dt(logits), R, V, _p(logits), ld, _p(rowstat), rowstat.stride(0) // 2, k, int(suppress_eos),
                                        eos_token_id, int(raw_logits), _p(row_bias), _p(top_val), _p(top_idx), _stream()), "mic_row_topk_tiles")
 
@@ -549,7 +556,14 @@ def row_flags(ids, n_ids, flags):
 
 
 def row_lse_topk(logits, ld, V, k, top_val, top_idx, R, *, forced_token=-1, suppress_eos=False, eos_token_id=2, raw_logits=False,
-                 row_bias=None):
+                 row_bias=None, token_map=None):
+    """token_map (int32 [V], ascending): the columns are a vocabulary shortlist — V, forced_token and eos_token_id count columns, top_idx
+    gets token_map[column]"""
+    if token_map is not None:
+        L.check(L.lib().mic_row_lse_topk_mapped(_dt(logits), R, V, _p(logits), ld, k, int(forced_token), int(suppress_eos), eos_token_id,
+                                                int(raw_logits), _p(row_bias), _p(top_val), _p(top_idx), _p(token_map), _stream()),
+                "mic_row_lse_topk_mapped")
+        return
     L.check(L.lib().mic_row_lse_topk(_dt(logits), R, V, _p(logits), ld, k, int(forced_token), int(suppress_eos), eos_token_id,
                                      int(raw_logits), _p(row_bias), _p(top_val), _p(top_idx), _stream()), "mic_row_lse_topk")
 
