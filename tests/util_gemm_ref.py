@@ -26,6 +26,13 @@ Error bound (`ref_epilogue` carries it along the same steps; every quantity is p
     R, C_old   e = e + u32 |v|
     C      |C - v| <= u_c |v| + (1 + u_c) e
 
+fp32 operands (gemm_f32_kernel, the parity mode; tests/test_gemm_f32_conformance_{cpu,gpu}.py): the products are no longer exact in
+fp32.  The kernel forms acc by K multiply-adds in ascending k (v_mfma_f32_32x32x2_f32), each of which rounds once when it is fused,
+so |err| <= K u |A||B| to first order and gamma_K = 2 K 2^-24 covers it with the same factor 2 (which also covers a multiply-add
+that rounds the product and the sum separately: 2 K roundings).  C_GAMMA, EPS_F and U32 are as for the bf16 kernels; u_c = u_z =
+2^-24 (c_dtype = z_dtype = "f32").  `emu_gemm` below restates that kernel contract in numpy fp32 (with a `defect=` switch: the
+checker has to reject what it is there for) and `check_problem` is the one comparison both modules run.
+
 u_c, u_z: the unit roundoff of the stored type, 2^-8 for bf16 (8 significant bits; round-to-nearest moves x by up to 2^-8 |x|,
 e.g. 1 + 2^-8 -> 1), 2^-24 for fp32.  eps_f = 32 * 2^-24: the fp32 evaluation error of erf / exp2 / rcp in act and act'.
 
@@ -278,3 +285,184 @@ def check_canary(t, window=None, what="C"):
     if n:
         idx = (bits != s).nonzero()[0].tolist()
         raise AssertionError(f"{what}: {n} element(s) outside the output window changed, first at {idx}")
+
+
+# ------------------------------------------------------------------------------------------------ fp32 GEMM (parity mode)
+# The kernel contract of gemm_f32_kernel + epilogue_store in numpy fp32, on the materialised problems of tests/util_gemm_f32_cases.py,
+# and the comparison of one problem with the fp64 reference.  The emulation reads the operand ALLOCATIONS through the kernel's own
+# strides and guards (so a wrong stride or guard meets the NaN padding), steps k by 16 in ascending order with one rounding per
+# multiply-add, and follows the header's epilogue order with the formulas of csrc/common.h on correctly rounded exp2 / rcp / erf.
+F32 = np.float32
+_LOG2E, _GELU_K1, _GELU_K2 = F32(1.4426950408889634), F32(1.5957691216057308), F32(0.07135481627261745)
+DEFECTS = ("k_tail_dropped", "col_past_k", "row_past_m", "ldz_for_r", "drop_idx_ldc", "alpha_after_bias", "bias_after_act",
+           "act_unrounded", "acc_ignored", "dact_wrong_id", "sam_sak_swapped", "gelu_tanh_nan")
+
+
+def _fma32(a, b, c):
+    """fp32 fused multiply-add through fp64: the product of two fp32 numbers is exact there, the sum rounds to 53 bits and then to
+    24 (the double rounding moves a result only when the 53-bit sum lies within 2^-29 ulp of an fp32 tie)"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (np.asarray(a, F32).astype(np.float64) * np.asarray(b, F32).astype(np.float64) + np.asarray(c, F32).astype(np.float64)).astype(F32)
+
+
+def _sigmoid_neg_log2(zl):
+    with np.errstate(over="ignore", under="ignore"):
+        return (F32(1) / (F32(1) + np.exp2(np.asarray(zl, F32).astype(np.float64)).astype(F32))).astype(F32)
+
+
+def _erf32(x):
+    return _erf(np.asarray(x, F32).astype(np.float64)).astype(F32)
+
+
+def emu_act_fwd(act, x, defect=None):
+    """act_fwd of csrc/common.h in fp32.  defect: 'gelu_tanh_nan' (NaN for x <= -64)"""
+    x = np.asarray(x, F32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        if act == 1:
+            return ((F32(0.5) * x) * (F32(1) + _erf32(x * F32(0.70710678118654752)))).astype(F32)
+        if act == 2:
+            p = _fma32(-_GELU_K2 * _LOG2E, x * x, -_GELU_K1 * _LOG2E)
+            y = (x * _sigmoid_neg_log2(x * p)).astype(F32)
+            return np.where(x <= -64, F32(np.nan), y) if defect == "gelu_tanh_nan" else y
+        if act == 3:
+            return (x * _sigmoid_neg_log2(x * (F32(-1.702) * _LOG2E))).astype(F32)
+    return x
+
+
+def emu_act_bwd(act, x):
+    """act_bwd of csrc/common.h in fp32"""
+    x = np.asarray(x, F32)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        if act == 1:
+            cdf = F32(0.5) * (F32(1) + _erf32(x * F32(0.70710678118654752)))
+            return (cdf + (x * F32(0.3989422804014327)) * np.exp(((F32(-0.5) * x) * x).astype(np.float64)).astype(F32)).astype(F32)
+        if act == 2:
+            x2 = x * x
+            s = _sigmoid_neg_log2(x * _fma32(-_GELU_K2 * _LOG2E, x2, -_GELU_K1 * _LOG2E))
+            return _fma32((x * s) * (F32(1) - s), _fma32(F32(3) * _GELU_K2, x2, _GELU_K1), s)
+        if act == 3:
+            s = _sigmoid_neg_log2(x * (F32(-1.702) * _LOG2E))
+            return _fma32((F32(1.702) * x) * s, F32(1) - s, s)
+    return np.ones_like(x)
+
+
+def canary_alloc(rows, ld):
+    return np.full((rows, ld), SENTINEL_F32, np.uint32).view(F32)
+
+
+def canary_intact(t, M, N) -> bool:
+    """every element of the fp32 allocation `t` outside [M][N] still holds the canary bits"""
+    bits = np.ascontiguousarray(t).view(np.uint32).copy()
+    bits[:M, :N] = SENTINEL_F32
+    return bool((bits == SENTINEL_F32).all())
+
+
+def _read(buf, idx):
+    """buf as the kernel sees it, a base pointer: flat[idx]; beyond the allocation reads NaN"""
+    flat = buf.reshape(-1)
+    ok = (idx >= 0) & (idx < flat.size)
+    return np.where(ok, flat[np.where(ok, idx, 0)], F32(np.nan)).astype(F32)
+
+
+def emu_gemm(h, defect=None):
+    """One materialised problem h (util_gemm_f32_cases.materialise) as the kernels compute it, in numpy fp32.  Returns the output
+    ALLOCATIONS {'C': [M + 2][ldc], 'Z': [M + 2][ldz] or None}, canary-filled outside what the emulated kernel wrote (bf16 problems:
+    Z holds bf16 values in fp32).  defect: one of DEFECTS —
+      k_tail_dropped   the K loop stops at K - K % 16            col_past_k       A's guard is gk <= K (B's is right)
+      row_past_m       every row guard is gm <= M                ldz_for_r        R read with ldz
+      drop_idx_ldc     dropout index m * ldc + n                 alpha_after_bias (acc + bias) * alpha
+      bias_after_act   act(acc * alpha) + bias                   act_unrounded    act on v, not on v rounded to the Z dtype
+      acc_ignored      C_old not added                           dact_wrong_id    act' of id 2 where 1 is asked
+      sam_sak_swapped  a k-major A read with its strides swapped gelu_tanh_nan    GELU-tanh gives NaN for x <= -64
+    A row past M read into the tile alone cannot change a valid output (the rows of a GEMM are independent): what shows is the kernel
+    that also stores that row, so `row_past_m` moves the guard of the load and of the store together and the canary catches it."""
+    from util_rowop_ref import mic_hash
+
+    assert defect is None or defect in DEFECTS, defect
+    M, N, K, f = h["M"], h["N"], h["K"], h["f"]
+    bf = h["dtype"] == "bf16"
+    rz = (lambda v: round_bf16(v).astype(F32)) if bf else (lambda v: v)
+    sam, sak = (1, h["lda"]) if h["akm"] else (h["lda"], 1)
+    if defect == "sam_sak_swapped" and h["akm"]:
+        sam, sak = sak, sam
+    sbk, sbn = (h["ldb"], 1) if h["bkm"] else (1, h["ldb"])
+    Mr = M + 1 if defect == "row_past_m" else M
+    Ka = K + 1 if defect == "col_past_k" else K
+    rows, cols = np.arange(Mr, dtype=np.int64), np.arange(N, dtype=np.int64)
+    acc = np.zeros((Mr, N), F32)
+    for k0 in range(0, K - K % 16 if defect == "k_tail_dropped" else K, 16):
+        for k in range(k0, min(k0 + 16, Ka)):
+            a = _read(h["A"], rows * sam + k * sak)
+            b = _read(h["B"], k * sbk + cols * sbn) if k < K else np.zeros(N, F32)
+            acc = _fma32(a[:, None], b[None, :], acc)
+    with np.errstate(invalid="ignore", over="ignore"):
+        m2, n2 = rows[:, None], cols[None, :]
+        alpha = F32(f.get("alpha", 1.0) or 1.0)
+        bias = None if h["bias"] is None else h["bias"][:N][None, :]
+        if bias is not None and defect == "alpha_after_bias":
+            v = ((acc + bias) * alpha).astype(F32)
+        else:
+            v = (acc * alpha).astype(F32)
+            if bias is not None and defect != "bias_after_act":
+                v = (v + bias).astype(F32)
+        out = {"C": canary_alloc(M + 2, h["ldc"]), "Z": None}
+        if f.get("zout"):
+            out["Z"] = canary_alloc(M + 2, h["ldz"])
+            out["Z"][:Mr, :N] = rz(v)
+        if f.get("act"):
+            v = emu_act_fwd(f["act"], v if defect == "act_unrounded" else rz(v), defect)
+            if bias is not None and defect == "bias_after_act":
+                v = (v + bias).astype(F32)
+        if f.get("dact"):
+            d = 2 if (defect == "dact_wrong_id" and f["dact"] == 1) else f["dact"]
+            v = (v * emu_act_bwd(d, _read(h["Zin"], m2 * h["ldz"] + n2))).astype(F32)
+        if f.get("drop"):
+            p = F32(f["drop"])
+            thr = np.uint32(min(float(p * F32(4294967296.0)), 4294967295.0))
+            idx = (m2 * (h["ldc"] if defect == "drop_idx_ldc" else N) + n2).astype(np.uint32)
+            v = np.where(mic_hash(h["seed"] & 0xFFFFFFFF, idx) >= thr, (v * (F32(1) / (F32(1) - p))).astype(F32), F32(0))
+        if h["R"] is not None:
+            v = (v + _read(h["R"], m2 * (h["ldz"] if defect == "ldz_for_r" else h["ldr"]) + n2)).astype(F32)
+        if h["C_old"] is not None:
+            out["C"][:M, :N] = h["C_old"]
+            if defect != "acc_ignored":
+                v = (v + out["C"][:Mr, :N]).astype(F32)
+        out["C"][:Mr, :N] = v
+    return out
+
+
+def same_bits(a, b) -> bool:
+    return np.array_equal(np.ascontiguousarray(a, F32).view(np.uint32), np.ascontiguousarray(b, F32).view(np.uint32))
+
+
+def check_problem(h, A, B, C, Z, label, *, log=True):
+    """One problem's outputs — the windows C [M][N] (fp32) and Z [M][N] or None — against the fp64 reference on the operand windows
+    A [M][K], B [K][N]; returns {'C': worst err / bound, 'Z': ...}.  With a stored Z the reference applies act to THAT z.
+    The sweeps of the fp32 kernel use the bare evaluation terms, forward eps_f (|z| + |act(z)|), backward eps_f (1 + |Zin|)^2 |v|
+    with v = acc = 1 (those of the bf16 kernels: the bound ref_epilogue carries); on every sweep no output is NaN or +-inf and the
+    forward Zout equals the exact pre-activation, rounded to the Z dtype, bit for bit."""
+    M, N, f = h["M"], h["N"], h["f"]
+    zd = "bf16" if h["dtype"] == "bf16" else "f32"
+    win = lambda t: None if t is None else np.asarray(t[:M, :N], np.float64)  # noqa: E731
+    epi = dict(alpha=f.get("alpha", 1.0), bias=None if h["bias"] is None else h["bias"][:N].astype(np.float64), act=f.get("act", 0),
+               dact=f.get("dact", 0), zin=win(h["Zin"]), R=win(h["R"]), C_old=win(h["C_old"]), c_dtype="f32", z_dtype=zd,
+               z_stored=None if Z is None else np.asarray(Z, np.float64))
+    if f.get("drop"):
+        epi["keep"], epi["drop_p"] = h["keep"], f["drop"]
+    with np.errstate(over="ignore"):  # exp(1.702 * 512) of the fp64 QuickGELU: inf, and the quotient 0
+        ref = gemm_ref(A, B, **epi)
+    bound = ref["bound_C"]
+    worst = {}
+    if f.get("sweep"):
+        assert np.isfinite(np.asarray(C, np.float64)).all(), f"{label}: NaN or inf on the activation grid"
+        if f["sweep"] == "fwd":
+            z = round_to(h["grid"] * f.get("alpha", 1.0), zd)
+            assert same_bits(Z, z), f"{label}: Zout is not the exact pre-activation"
+            if zd == "f32":
+                bound = EPS_F * (np.abs(z) + np.abs(ref["C"]))
+        elif zd == "f32":
+            bound = EPS_F * (1 + np.abs(h["grid"])) ** 2
+    if Z is not None:
+        worst["Z"] = check(Z, ref["Z"], ref["bound_Z"], f"{label} Zout", log=log)
+    worst["C"] = check(C, ref["C"], bound, f"{label} C", log=log)
+    return worst
