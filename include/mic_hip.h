@@ -610,6 +610,22 @@ int mic_sample_rows(int dtype, int R, int V, const void* logits, int ld, uint32_
 int mic_warp_thresholds(int dtype, int R, int V, const void* logits, int ld, float temperature, int suppress_eos,
                         int eos_token_id, int top_k, float top_p, float* thr, int32_t* tie_limit, void* stream);
 
+/* mic_sample_rows_keyed: `draws` independent categorical draws per image in one launch — generate(do_sample=True,
+ *   num_return_sequences=draws): the `_sample` loop of gen:537-663 run `draws` times over the same images, each run with its own key
+ *   (the N-best counterpart for beam search, gen:980-990 read at more than one column, is host code).  logits is [images * draws][ld],
+ *   row r = image * draws + n.  Row r is row `image` of a mic_sample_rows call over `images` rows with key (keys[2n], keys[2n + 1]):
+ *   keys is a DEVICE array uint32 [draws][2], and the threefry counters are those of an [images][V] array (images * V < 2^32 is
+ *   checked, not rows * V).  temperature, forced_token, suppress_eos, min_keep / tie_limit ([images * draws], per row) as in
+ *   mic_sample_rows; with draws == 1 the ids are bit for bit that entry point's.  Entries that are -inf after suppression and
+ *   thresholds get no noise (their sum is -inf whatever the noise); a row in which nothing survives draws index 0.
+ *   score (optional, float [images * draws]): score[r] += log p(drawn token) under the distribution the draw was made from — the
+ *   softmax over the surviving entries of logits / temperature, as an fp32 online (max, sum-exp) merged in a fixed order (the same
+ *   bytes give the same bits) — unless finished[r] != 0 (optional, int32 [images * draws], read before mic_greedy_step updates it,
+ *   so the EOS draw itself counts).  A forced token is a point mass: score is left alone. */
+int mic_sample_rows_keyed(int dtype, int images, int draws, int V, const void* logits, int ld, const uint32_t* keys,
+                          float temperature, int forced_token, int suppress_eos, int eos_token_id, const float* min_keep,
+                          const int32_t* tie_limit, int32_t* out_idx, const int32_t* finished, float* score, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Input pipeline: the reference's image Transform (main.py:165-179; evaluation.py:35-60) + the
  * NCHW->NHWC permute of collate_fn (main.py:494) for a batch of uint8 images of arbitrary sizes:

@@ -2,6 +2,7 @@
 // the beam-search bookkeeping of gen:857-966 (K17) as ONE small kernel per step; the KV cache is never gathered
 // (K18) — a [rows][max_len] slot-ownership table is updated instead (see attention.hip / mic_attn_decode).
 #include "common.h"
+#include "threefry.h"
 
 #define TOPK_MAX 16   // widest top-k of the partials-based kernel (row_topk_tiles: k = 2 * num_beams <= 16, its candidate set lives in registers)
 #define TOPK_WIDE 64  // widest top-k of the streaming kernel and of the beam bookkeeping: num_beams <= 32
@@ -635,20 +636,6 @@ __global__ void fill_i32_kernel(int32_t* p, int n, int v) {
 //   uniform = max(tiny, (bitcast(bits >> 9 | 0x3f800000) - 1) * (1 - tiny) + tiny)        (random.uniform, minval=tiny)
 //   gumbel  = -log(-log(uniform)).
 // One block per row; ties resolve to the lowest index (jnp.argmax).
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-__device__ __forceinline__ void threefry2x32(uint32_t k0, uint32_t k1, uint32_t& x0, uint32_t& x1) {
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  const int R[2][4] = {{13, 15, 26, 6}, {17, 29, 16, 24}};
-  x0 += ks[0]; x1 += ks[1];
-#pragma unroll
-  for (int g = 0; g < 5; ++g) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { x0 += x1; x1 = rotl32(x1, R[g & 1][i]); x1 ^= x0; }
-    x0 += ks[(g + 1) % 3];
-    x1 += ks[(g + 2) % 3] + (uint32_t)(g + 1);
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(1024) void sample_rows_kernel(int R, int V, const T* __restrict__ logits, int ld, uint32_t k0,
                                                            uint32_t k1, float temperature, int suppress_eos, int eos,
@@ -663,14 +650,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(int R, int V, const T
   int bi = 0x7fffffff;
   for (int i = threadIdx.x; i < V; i += blockDim.x) {
     const uint32_t e = (uint32_t)row * (uint32_t)V + (uint32_t)i;
-    uint32_t c0, c1;
-    if (e < h) { c0 = e; c1 = e + h < n ? e + h : 0u; } else { c0 = e - h; c1 = e; }
-    threefry2x32(k0, k1, c0, c1);
-    const uint32_t bits = e < h ? c0 : c1;
-    const float f = __uint_as_float((bits >> 9) | 0x3f800000u) - 1.0f;
-    const float tiny = 1.17549435e-38f;
-    const float u = fmaxf(tiny, f * (1.0f - tiny) + tiny);
-    const float g = -logf(-logf(u));
+    const float g = gumbel_noise(k0, k1, e, h, n);
     float v = ElemT<T>::ld(x + i);
     if (temperature != 1.0f) v = v / temperature;
     if ((suppress_eos && i == eos) || v < thr || (v == thr && i >= lim)) v = -INFINITY;

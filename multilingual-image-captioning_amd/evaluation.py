@@ -114,19 +114,20 @@ def vocabulary_shortlist(id_arrays, always=()) -> np.ndarray:
 
 
 def generate_languages(model, pixel_values, lang_ids: Dict[str, int], *, via: str = "forced_bos", max_length: int = 64,
-                       num_beams: int = 4, allowed_token_ids=None) -> Dict[str, np.ndarray]:
+                       num_beams: int = 4, allowed_token_ids=None, num_return_sequences=None) -> Dict[str, np.ndarray]:
     """Captions of the same images in every language of `lang_ids` ({"en_XX": id, ...}) from ONE `generate` call: the language
     ids go in as a sequence, the images are encoded once and all languages share one decode chain; the result per language is
     that of its own call (`evaluation.py:80-94` calls generate once per language).  `via` names the argument that selects the
     language: "forced_bos" (`forced_bos_token_id`) or "decoder_start" (`decoder_start_token_id`, main.py:820).
     `allowed_token_ids`: the vocabulary shortlist of `generate`, shared by all languages (see `vocabulary_shortlist`).
-    Returns {language: int32 ids [batch, max_length]}.  `evaluate()` keeps one call per language: its loaders carry different
+    `num_return_sequences=N`: the N best beam hypotheses per image and language, best first (row image * N + j), see `generate`.
+    Returns {language: int32 ids [batch, max_length]} ([batch * N, max_length] with N).  `evaluate()` keeps one call per language: its loaders carry different
     images per language."""
     arg = {"forced_bos": "forced_bos_token_id", "decoder_start": "decoder_start_token_id"}.get(via)
     if arg is None:
         raise ValueError(f"via={via!r}: expected 'forced_bos' or 'decoder_start'")
     langs = list(lang_ids)
     gen = model.generate(pixel_values, max_length=max_length, num_beams=num_beams, allowed_token_ids=allowed_token_ids,
-                         **{arg: [int(lang_ids[l]) for l in langs]})
+                         num_return_sequences=num_return_sequences, **{arg: [int(lang_ids[l]) for l in langs]})
     seq = np.asarray(gen.sequences.cpu())
     return {l: seq[g] for g, l in enumerate(langs)}

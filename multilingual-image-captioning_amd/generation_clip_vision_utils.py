@@ -31,9 +31,15 @@ Vocabulary shortlist (`generate(allowed_token_ids=A)`): the head GEMM runs over 
 the candidates leave as vocabulary ids, so `mic_beam_step` / `mic_greedy_step` and the embedding lookup of the next step see no
 difference, and the step has the same number of launches.  A decode plan is keyed by the shortlist's identity and keeps the object
 alive: captured steps hold its tensors' addresses, the column count and the EOS column.
+
+Several captions per image (`generate(num_return_sequences=N)`): sampling runs its N draws per image as one chain of images x N rows from
+a decode plan (`_sample_group`: `mic_sample_rows_keyed` reads the N keys of the step from a device table and adds each draw's
+log-probability to the row's score); beam search returns the N best of the K hypotheses it ends with (`_n_best`: gen:987-990 at more than
+one column).  None or 1 leaves `_sample` and the beam post-processing the code they were.
 """
 from __future__ import annotations
 
+import operator
 from typing import Optional
 
 import torch
@@ -158,6 +164,31 @@ def normalize_allowed_token_ids(allowed_token_ids, vocab_size: int, *, eos_token
     return ids
 
 
+def normalize_num_return_sequences(num_return_sequences, *, do_sample: bool, num_beams: int) -> int:
+    """`generate(num_return_sequences=N)` -> N (1 for None).  What `generate` refuses without the argument keeps its error and message
+    and comes first (beam sampling, gen:336; num_beams > 32).  ValueError: N not an integer (a bool is not one) or < 1, N > 1 with
+    greedy search (one image has one greedy caption), N > num_beams for a beam search (it ends with num_beams hypotheses per image)."""
+    if num_return_sequences is None:
+        return 1
+    if do_sample and num_beams > 1:
+        raise NotImplementedError("`Beam sampling is currently not implemented.")  # gen:336
+    if not do_sample and 2 * num_beams > 64:
+        raise NotImplementedError("num_beams > 32 needs a wider per-row top-k than this build ships (k = 2*num_beams <= 64)")
+    try:
+        if isinstance(num_return_sequences, bool):
+            raise TypeError
+        N = operator.index(num_return_sequences)
+    except TypeError:
+        raise ValueError(f"`num_return_sequences` must be an integer >= 1, got {num_return_sequences!r}") from None
+    if N < 1:
+        raise ValueError(f"`num_return_sequences` must be an integer >= 1, got {N}")
+    if N > 1 and not do_sample and num_beams == 1:
+        raise ValueError(f"num_return_sequences={N} with greedy search: one image has one greedy caption; use do_sample=True or num_beams >= {N}")
+    if not do_sample and N > num_beams:
+        raise ValueError(f"num_return_sequences={N} exceeds num_beams={num_beams}: a beam search ends with num_beams hypotheses per image")
+    return N
+
+
 class _DecodePlan:
     """Fixed-address device state of one generate configuration + its captured decoder steps."""
 
@@ -239,7 +270,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
                  num_beams: Optional[int] = None, no_repeat_ngram_size: Optional[int] = None, min_length: Optional[int] = None,
                  forced_bos_token_id: Optional[int] = None, forced_eos_token_id: Optional[int] = None,
                  length_penalty: Optional[float] = None, early_stopping: Optional[bool] = None, trace: bool = True,
-                 params=None, allowed_token_ids=None, **model_kwargs):
+                 params=None, allowed_token_ids=None, num_return_sequences: Optional[int] = None, **model_kwargs):
         """`FlaxCLIPVisionGenerationMixin.generate` (gen:128-336): same arguments, defaults from `config.mbart_config`, same dispatch —
         greedy (`num_beams == 1`, no sampling), sampling (`do_sample`, one beam) or beam search; `input_ids` = pixel values.
         Limits of this build (the reference has none of the first two; the third is the reference's own): `num_beams <= 32` — the fused
@@ -263,7 +294,23 @@ class FlaxCLIPVisionMBartGenerationMixin:
         kept on the model; refreshed in place when the weights move).  `eos_token_id`, a scalar forced BOS / EOS id in force, every
         per-language BOS id and, for beam search, len(A) >= 2 * num_beams are required of A (ValueError, before any device work); start ids
         and PAD need not be in it.  One set per call (the languages of a grouped call share it); `do_sample=True` raises
-        NotImplementedError.  None (default): the whole vocabulary."""
+        NotImplementedError.  None (default): the whole vocabulary.
+
+        Several captions per image: `num_return_sequences=N` (the argument and output layout of the PyTorch `generate`; the reference's
+        Flax `generate` has none).  None or 1: every path is what it is without the argument.  Sampling (`do_sample=True`, one beam,
+        N >= 2): N independent draws per image from ONE decode chain — `keys = jax.random.split(PRNGKey(prng_key), N)`, and draw n is
+        what `generate(same arguments, prng_key=keys[n])` returns (float32: token ids bit for bit; both sampling modes).  Returns
+        `sequences [B*N, max_length]` (row image * N + n) and `scores [B*N]`: the log-likelihood of each caption as drawn — the sum over
+        its steps, the EOS draw included, of log p(token) under the distribution the draw was made from (raw logits in the reference's
+        mode, the processed and warped ones with `sample_from_processed_logits=True`; a forced token adds 0).  The images are encoded
+        once, cross K/V projected once per image, the state lives in a decode plan (MIC_DECODE_GRAPHS=1 replays the steps; the per-step
+        keys are a device table, so a warm plan serves any `prng_key`).  Beam search (`num_beams = K`, 1 <= N <= K): the N best of the K
+        hypotheses the search ends with, best first — `sequences [B*N, max_length]`, `scores [B*N]`, row image * N + j = gen:980-990 read
+        at column K-1-j instead of -1 (row j = 0 is the plain call's result bit for bit; `out["steps"]` is unchanged); with a sequence
+        of language ids `[G, B*N, max_length]` and `[G, B*N]`.  Slots that never held a finished hypothesis come back as they lie in
+        the state: an image with fewer than N finished hypotheses returns PAD rows with the score -1e7 for the rest (an image with none
+        returns its running hypotheses).  ValueError, before the encoder runs: N < 1 or not an integer, N > 1 with greedy search,
+        N > num_beams."""
         mc = self.config.mbart_config
         G, bos_ids, start_ids, grouped = normalize_language_ids(decoder_start_token_id, forced_bos_token_id)
         if grouped:  # resolved per language below; the scalar code in between sees "not given"
@@ -301,6 +348,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
                 forced_bos_token_id=None if lang else (forced_bos_token_id if forced_bos_token_id is not None else mc.forced_bos_token_id),
                 forced_eos_token_id=forced_eos_token_id if forced_eos_token_id is not None else mc.forced_eos_token_id,
                 language_bos_ids=lang["bos"] if lang else None, num_beams=num_beams, do_sample=bool(do_sample))
+        N = normalize_num_return_sequences(num_return_sequences, do_sample=bool(do_sample), num_beams=num_beams)  # host-only, before the encoder runs
         # gen:109-120: `params=` is NOT forwarded to encode (the encoder always uses self.params); the decoder uses it.
         enc = self.encode(input_ids, return_dict=True, **{k: v for k, v in model_kwargs.items()
                                                           if not (k.startswith("decoder_") or k.startswith("cross_attn"))})
@@ -321,6 +369,9 @@ class FlaxCLIPVisionMBartGenerationMixin:
             top_k = top_k if top_k is not None else getattr(mcfg, "top_k", 50)  # gen:349-356
             top_p = top_p if top_p is not None else getattr(mcfg, "top_p", 1.0)
             temperature = temperature if temperature is not None else getattr(mcfg, "temperature", 1.0)
+            if N > 1:
+                return self._sample_group(ehs, B, N, decoder_start_token_id, max_length, pad_token_id, eos_token_id, prng_key, procs,
+                                          dict(top_k=top_k, top_p=top_p, temperature=temperature), from_processed)
             return self._sample(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, prng_key, procs,
                                 dict(top_k=top_k, top_p=top_p, temperature=temperature),
                                 from_processed)
@@ -328,7 +379,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
             length_penalty = length_penalty if length_penalty is not None else mc.length_penalty  # gen:733-742
             early_stopping = early_stopping if early_stopping is not None else mc.early_stopping
             return self._beam_search(ehs, B, num_beams, decoder_start_token_id, max_length, pad_token_id, eos_token_id,
-                                     length_penalty, early_stopping, procs, lang, sl)
+                                     length_penalty, early_stopping, procs, lang, sl, n_best=N)
         else:
             raise NotImplementedError("`Beam sampling is currently not implemented.")  # gen:336
 
@@ -527,6 +578,82 @@ class FlaxCLIPVisionMBartGenerationMixin:
             cur_len += 1
         return ModelOutput(sequences=sequences)
 
+    def _sample_group(self, ehs, n_img, N, start_token, max_length, pad_token_id, eos_token_id, prng_key, procs, warp, from_processed: bool):
+        """generate(do_sample=True, num_return_sequences=N >= 2): N `_sample` calls over the same images — call n with the key
+        `split(PRNGKey(prng_key), N)[n]` — as one decode chain of n_img * N rows, row = image * N + n (cross K/V per image: row_div = N).
+        mic_sample_rows_keyed gives row (image, n) the noise of row `image` of call n.  Call n alone would stop once ITS rows have all
+        finished (gen:596-603); here its rows ride along until every row has: a finished row only ever receives PAD (gen:629-642) into a
+        buffer that is PAD already and leaves its score alone, so that changes nothing (the argument `_greedy_search` relies on).  The
+        per-step keys of all draws are walked on the host before the chain starts and copied into the plan's [max_length][N][2] table:
+        the step at cur_len reads its N keys from device memory, a captured step holds the table's address, not a call's keys."""
+        from . import prng
+        from .modeling_clip_vision_mbart import ModelOutput
+
+        dev, st = self.device, self.store
+        R = n_img * N
+        use_k = from_processed and warp["top_k"] not in (None, 0)
+        use_p = from_processed and warp["top_p"] is not None and warp["top_p"] < 1.0
+        temp = float(warp["temperature"] or 1.0) if from_processed else 1.0
+
+        def build(plan):
+            t = plan.t
+            t["sequences"] = torch.empty((R, max_length), dtype=torch.int32, device=dev)
+            t["finished"] = torch.empty(R, dtype=torch.int32, device=dev)
+            t["next_token"] = torch.empty((R,), dtype=torch.int32, device=dev)
+            t["drawn"] = torch.empty((R, 1), dtype=torch.int32, device=dev)
+            t["scores"] = torch.empty(R, dtype=torch.float32, device=dev)
+            t["keys"] = torch.empty((max_length, N, 2), dtype=torch.int32, device=dev)  # the uint32 key words, bit for bit
+            t["pos_all"] = torch.arange(max_length, dtype=torch.int32, device=dev).repeat_interleave(R)
+            if use_k or use_p:
+                t["thr"] = torch.empty(R, dtype=torch.float32, device=dev)
+                t["lim"] = torch.empty(R, dtype=torch.int32, device=dev)
+
+        plan = self._decode_plan(("sample", n_img, N, max_length, pad_token_id, eos_token_id,
+                                  (procs["min_length"], procs["forced_bos"], procs["forced_eos"]),
+                                  (warp["top_k"] if use_k else 0, float(warp["top_p"]) if use_p else 1.0, temp), bool(from_processed), self.dtype), build)
+        t = plan.t
+        sequences, finished, next_token, drawn, scores, keys, pos_all = (t[k] for k in ("sequences", "finished", "next_token", "drawn", "scores",
+                                                                                        "keys", "pos_all"))
+        thr, lim = t.get("thr"), t.get("lim")
+        table = prng.step_key_table(prng.split(prng.prng_key(0 if prng_key is None else prng_key), N), max_length)  # gen:561, 610 per draw
+        keys.copy_(torch.from_numpy(table.view("int32")))
+        sequences.fill_(pad_token_id)
+        sequences[:, 0].fill_(start_token)
+        next_token.fill_(start_token)
+        finished.zero_()
+        scores.zero_()
+        cache = self._plan_cache(plan, R, max_length)
+        self._decode_set_encoder(cache, ehs.reshape(n_img * st.S, st.d), n_img, N)
+        use_graphs = _graphs_enabled(dev)
+
+        def step(cur_len):
+            def fn():
+                with ops.pinned_stream():
+                    cache["cache_index"] = cur_len - 1
+                    logits = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R])
+                    kw = dict(finished=finished, score=scores)
+                    if from_processed:
+                        forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
+                        if thr is not None and forced < 0:  # gen:338-366: temperature -> top-k -> top-p, as (threshold, tie limit) per row
+                            ops.warp_thresholds(logits, logits.stride(0), st.V, thr, lim, R, temperature=temp, suppress_eos=suppress,
+                                                eos_token_id=eos_token_id, top_k=warp["top_k"] if use_k else 0,
+                                                top_p=warp["top_p"] if use_p else 1.0)
+                        kw.update(temperature=temp, forced_token=forced, suppress_eos=suppress, eos_token_id=eos_token_id, min_keep=thr,
+                                  tie_limit=lim)
+                    # (the reference's mode: jax.random.categorical(prng_key, model_outputs.logits[:, -1]), gen:625-627 — no processors)
+                    ops.sample_rows_keyed(logits, logits.stride(0), st.V, keys[cur_len], drawn, n_img, N, **kw)
+                    ops.greedy_step(R, max_length, cur_len, eos_token_id, pad_token_id, drawn, 1, sequences, finished, next_token)  # gen:629-642
+            return fn
+
+        cur_len = 1
+        while cur_len < max_length:
+            if (cur_len - 1) % _POLL == 0 and cur_len > 1 and bool(finished.all().item()):
+                break
+            plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)  # (step 1 stays eager, as in the other plans)
+            cur_len += 1
+        plan.calls += 1
+        return ModelOutput(sequences=sequences.clone(), scores=scores.clone())
+
     # ------------------------------------------------------------------ gen:665-990
     def _decode_slices(self, B: int, K: int) -> int:
         """Number of independent image slices a beam search is cut into (opt-in experiment, default 1 = off).  Images do not interact
@@ -550,10 +677,11 @@ class FlaxCLIPVisionMBartGenerationMixin:
         return max(n, 1)
 
     def _beam_search(self, ehs, B, K, start_token, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, lang=None,
-                     sl=None):
+                     sl=None, n_best: int = 1):
         """lang = None: one search over B images.  lang = dict(G, start, bos): G searches over the same n_img images in one unsliced
         chain — bookkeeping item i = image * G + g belongs to search g (mic_beam_step_groups), its K rows share the image's cross K/V
-        with the rows of the other searches (row_div = G * K)."""
+        with the rows of the other searches (row_div = G * K).  n_best = N >= 2 (generate(num_return_sequences=N)): the search is the
+        same; the result is read at the N best of its K final hypotheses instead of the best alone (host code only)."""
         from .modeling_clip_vision_mbart import ModelOutput
 
         if 2 * K > 64:
@@ -666,6 +794,13 @@ class FlaxCLIPVisionMBartGenerationMixin:
             plan.calls += 1
             t = plan.subs[0].t
             any_fin = t["finished"].bool().any(dim=1)  # gen:980-990, as below
+            if n_best > 1:
+                out_seq, out_scores = self._n_best(torch.where(any_fin[:, None, None], t["seq"], t["running_seq"]),
+                                                   torch.where(any_fin[:, None], t["scores"], t["running_scores"]), n_best)
+                out = ModelOutput(sequences=out_seq.view(n_img, G, n_best, max_length).transpose(0, 1).reshape(G, n_img * n_best, max_length),
+                                  scores=out_scores.view(n_img, G, n_best).transpose(0, 1).reshape(G, n_img * n_best))
+                out["steps"] = [int(v) for v in gs[:, 4].tolist()]
+                return out
             out_seq = torch.where(any_fin[:, None, None], t["seq"], t["running_seq"])[:, -1]
             out_scores = torch.where(any_fin[:, None], t["scores"], t["running_scores"])[:, -1]
             out = ModelOutput(sequences=out_seq.view(n_img, G, max_length).transpose(0, 1).contiguous(),
@@ -686,10 +821,21 @@ class FlaxCLIPVisionMBartGenerationMixin:
             any_fin = t["finished"].bool().any(dim=1)  # gen:980
             out_seq = torch.where(any_fin[:, None, None], t["seq"], t["running_seq"])  # gen:981-983
             out_scores = torch.where(any_fin[:, None], t["scores"], t["running_scores"])  # gen:984
+            if n_best > 1:
+                out_seq, out_scores = self._n_best(out_seq, out_scores, n_best)
+                outs.append((out_seq.reshape(-1, max_length), out_scores.reshape(-1)))
+                continue
             outs.append((out_seq[:, -1], out_scores[:, -1]))  # gen:987-990
         out = ModelOutput(sequences=torch.cat([o[0] for o in outs]).contiguous(), scores=torch.cat([o[1] for o in outs]).contiguous())
         out["steps"] = steps
         return out
+
+    @staticmethod
+    def _n_best(out_seq, out_scores, n_best: int):
+        """gen:987-990 at columns K-1, K-2, ..., K-n_best instead of -1: the state is sorted ascending (best last), so the n_best best
+        hypotheses of every item, best first — [items, n_best, max_length] and [items, n_best].  Slots that never held a finished
+        hypothesis come back as they lie in the state (PAD rows, score NEG)."""
+        return out_seq.flip(1)[:, :n_best].contiguous(), out_scores.flip(1)[:, :n_best].contiguous()
 
     def _beam_step_fn(self, cache, t, B, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, groups=None,
                       bos_rows=None, sl=None):

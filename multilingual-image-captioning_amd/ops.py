@@ -601,6 +601,17 @@ def sample_rows(logits, ld, V, key, out_idx, R, *, temperature=1.0, forced_token
                                     _p(out_idx), _stream()), "mic_sample_rows")
 
 
+def sample_rows_keyed(logits, ld, V, keys, out_idx, images, draws, *, temperature=1.0, forced_token=-1, suppress_eos=False, eos_token_id=2,
+                      min_keep=None, tie_limit=None, finished=None, score=None):
+    """mic_sample_rows_keyed: row image * draws + n of the [images * draws][ld] logits draws with keys[n] — keys a device tensor of
+    `draws` pairs of 32-bit key words (int32 storage of the uint32 bits).  score[r] += log p(drawn) unless finished[r]."""
+    if keys.dtype != torch.int32 or keys.numel() != 2 * draws or not keys.is_contiguous():
+        raise L.MicError(f"sample_rows_keyed: keys must be a contiguous int32 tensor of {draws} x 2 key words")
+    L.check(L.lib().mic_sample_rows_keyed(_dt(logits), images, draws, V, _p(logits), ld, _p(keys), float(temperature), int(forced_token),
+                                          int(suppress_eos), eos_token_id, _p(min_keep), _p(tie_limit), _p(out_idx), _p(finished),
+                                          _p(score), _stream()), "mic_sample_rows_keyed")
+
+
 def warp_thresholds(logits, ld, V, thr, tie_limit, R, *, temperature=1.0, suppress_eos=False, eos_token_id=2, top_k=0, top_p=1.0):
     L.check(L.lib().mic_warp_thresholds(_dt(logits), R, V, _p(logits), ld, float(temperature), int(suppress_eos), eos_token_id,
                                         int(top_k or 0), float(top_p if top_p is not None else 1.0), _p(thr), _p(tie_limit), _stream()),

@@ -39,3 +39,14 @@ def split(key, num: int = 2) -> np.ndarray:
     cnt = np.arange(2 * num, dtype=U)
     a, b = threefry2x32(key, cnt[:num], cnt[num:])
     return np.concatenate([a, b]).reshape(num, 2)
+
+
+def step_key_table(keys, max_length: int) -> np.ndarray:
+    """uint32 [max_length][N][2]: entry [cur_len][n] is the key the step at `cur_len` of a `_sample` call started from keys[n] draws
+    with — each draw walks `k, key = split(key)` once per step (gen:610), cur_len = 1 .. max_length - 1; row 0 is unused (zeros)."""
+    keys = np.asarray(keys, dtype=U).reshape(-1, 2)
+    table = np.zeros((max_length, keys.shape[0], 2), dtype=U)
+    for n, key in enumerate(keys):
+        for cur_len in range(1, max_length):
+            table[cur_len, n], key = split(key)
+    return table

@@ -2,7 +2,8 @@
 Makefile leaves in csrc/build/<unit>.res): VGPRs / AGPRs / SGPRs, scratch, spills, occupancy (waves per SIMD), static LDS.
 
   python tools/kernel_resources.py            table of the current build beside the committed one, differences marked
-  python tools/kernel_resources.py --update   rewrite tests/golden/kernel_resources.json from the current build
+  python tools/kernel_resources.py --update   rewrite tests/golden/kernel_resources.json from the current build (and
+                                              tests/golden/kernel_resources_units.json from csrc/build/units/: the Makefile's UNIT_SRCS)
 
 The guard (tests/test_kernel_resources_cpu.py) fails on scratch or spills in any kernel, on an occupancy below the committed one, and
 on kernels the table does not know — the two silent regressions of round 4 (272 B of scratch in the non-PLAIN 256x256 epilogues, a
@@ -16,6 +17,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "multilingual-image-captioning_amd", "csrc", "build")
 TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources.json")
+# units whose kernels are not in that table (the Makefile's UNIT_SRCS): their listings lie under build/units/, their table is this one
+UNITS_BUILD = os.path.join(BUILD, "units")
+UNITS_TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources_units.json")
 FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
           "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
 
@@ -55,12 +59,12 @@ def short(name: str) -> str:
     return re.sub(r"\(.*$", "", name)  # template arguments stay, the parameter list goes
 
 
-def current():
-    """{unit: {kernel (demangled, short): fields}} of the build directory"""
+def current(build=BUILD):
+    """{unit: {kernel (demangled, short): fields}} of a build directory"""
     units = {}
-    for f in sorted(os.listdir(BUILD)) if os.path.isdir(BUILD) else []:
+    for f in sorted(os.listdir(build)) if os.path.isdir(build) else []:
         if f.endswith(".res"):
-            k = parse_res(os.path.join(BUILD, f))
+            k = parse_res(os.path.join(build, f))
             dm = demangle(list(k))
             units[f[:-4]] = {short(dm[n]): v for n, v in k.items()}
     return units
@@ -93,21 +97,23 @@ def compare(cur, ref):
 
 
 def main():
-    cur = current()
+    cur, cur_units = current(), current(UNITS_BUILD)
     if not cur:
         sys.exit(f"no .res files under {BUILD}: build first (make -C multilingual-image-captioning_amd/csrc)")
     if "--update" in sys.argv:
         os.makedirs(os.path.dirname(TABLE), exist_ok=True)
-        json.dump(cur, open(TABLE, "w"), indent=0, sort_keys=True)
-        print(f"wrote {TABLE}: {sum(len(v) for v in cur.values())} kernels in {len(cur)} units")
+        for table, c in ((TABLE, cur), (UNITS_TABLE, cur_units)):
+            json.dump(c, open(table, "w"), indent=0, sort_keys=True)
+            print(f"wrote {table}: {sum(len(v) for v in c.values())} kernels in {len(c)} units")
         return
-    ref = json.load(open(TABLE)) if os.path.exists(TABLE) else {}
     print(f"{'unit':<12} {'kernel':<88} {'vgpr':>4} {'agpr':>4} {'sgpr':>4} {'scr':>4} {'occ':>3} {'lds':>6}")
-    for unit, ks in cur.items():
-        for name, v in sorted(ks.items()):
-            print(f"{unit:<12} {name[:88]:<88} {v.get('vgpr', 0):>4} {v.get('agpr', 0):>4} {v.get('sgpr', 0):>4} {v.get('scratch', 0):>4} {v.get('occupancy', 0):>3} {v.get('lds', 0):>6}")
-    for sev, m in compare(cur, ref):
-        print(f"[{sev}] {m}")
+    for table, c in ((TABLE, cur), (UNITS_TABLE, cur_units)):
+        ref = json.load(open(table)) if os.path.exists(table) else {}
+        for unit, ks in c.items():
+            for name, v in sorted(ks.items()):
+                print(f"{unit:<12} {name[:88]:<88} {v.get('vgpr', 0):>4} {v.get('agpr', 0):>4} {v.get('sgpr', 0):>4} {v.get('scratch', 0):>4} {v.get('occupancy', 0):>3} {v.get('lds', 0):>6}")
+        for sev, m in compare(c, ref):
+            print(f"[{sev}] {m}")
 
 
 if __name__ == "__main__":
