@@ -19,7 +19,9 @@ place per call (no 3 GB cache allocation + zero fill per generate call).  With `
 additionally captures step t of the loop into a hipGraph (one graph per step index: the cache slot, the valid length and the
 processor switches are baked-in launch arguments) and from then on a step is ONE graph launch.  The host never waits inside
 the loop except for a stop-flag poll every 8 steps (`lax.while_loop` in the reference has no host in it either, gen:976).
-MEASURED (MI355X, ROCm 7.2, tools/decode_host_probe.py, ms per decoder step, graphs vs eager): batch 256 x 4 beams 2.71 vs
+One driver, `_run_chain`, owns that loop for greedy search, beam search (sliced, unsliced, grouped) and grouped sampling: a strategy
+hands it the launches of one step and its host stop test.
+MEASURED (MI355X, ROCm 7.2, with a host-side probe that is no longer in the tree, ms per decoder step, graphs vs eager): batch 256 x 4 beams 2.71 vs
 2.70 (GPU-bound either way), batch 32: 1.61 vs 1.62, batch 4: 1.47 vs 1.57 — a replayed 140-node graph costs what 140
 back-to-back launches cost: the ~10 us per dependent kernel are the kernels' own durations (a chain of first-tile miss, K loop,
 reduction and epilogue), not launch overhead, so the graphs are correct (tests) but buy nothing for a single chain and stay
@@ -34,8 +36,9 @@ alive: captured steps hold its tensors' addresses, the column count and the EOS 
 
 Several captions per image (`generate(num_return_sequences=N)`): sampling runs its N draws per image as one chain of images x N rows from
 a decode plan (`_sample_group`: `mic_sample_rows_keyed` reads the N keys of the step from a device table and adds each draw's
-log-probability to the row's score); beam search returns the N best of the K hypotheses it ends with (`_n_best`: gen:987-990 at more than
-one column).  None or 1 leaves `_sample` and the beam post-processing the code they were.
+log-probability to the row's score; the step body, `_sample_step_fn`, is the one `_sample` runs with `mic_sample_rows` and a host
+key); beam search returns the N best of the K hypotheses it ends with (`_beam_result` / `_n_best`: gen:987-990 at N columns, N = 1
+being the plain call).  None or 1 leaves `_sample` the mechanism it was.
 """
 from __future__ import annotations
 
@@ -107,8 +110,6 @@ def normalize_language_ids(decoder_start_token_id=None, forced_bos_token_id=None
             out.append(None)
         else:
             try:
-                import operator
-
                 out.append([operator.index(raw.item() if hasattr(raw, "item") else raw)] * G)
             except (TypeError, ValueError):
                 raise ValueError(f"`{name}`: expected an integer or a sequence of integers, got {raw!r}") from None
@@ -261,6 +262,20 @@ def _graphs_enabled(dev, slices: int = 1) -> bool:
     return want == "1" or slices > 1
 
 
+def _run_chain(plan: _DecodePlan, step, max_length: int, stopped, use_graphs: bool) -> None:
+    """The decode chain of one call on `plan`: `step(cur_len)` issues the launches of decoder step cur_len = 1 .. max_length - 1 on
+    the current stream; `stopped()` is the strategy's host test (one device read) that every row / every search is done.  A step
+    issued after that point changes nothing — greedy and sampling: a finished row only ever receives PAD (gen:501-507, 629-642) into
+    a buffer that is PAD already; beam search: mic_beam_step evaluates `beam_search_cond_fn` (gen:798-820) on the device and is a
+    no-op once it said stop — so the host enqueues steps (graph replays once the plan is warm) without waiting and asks only every
+    _POLL steps: in front of steps _POLL + 1, 2 * _POLL + 1, ...  Step 1 carries the call's forced-BOS id and is never captured."""
+    for cur_len in range(1, max_length):
+        if cur_len > 1 and (cur_len - 1) % _POLL == 0 and stopped():
+            break
+        plan.run_step(cur_len, lambda: step(cur_len), use_graphs and cur_len > 1)
+    plan.calls += 1
+
+
 class FlaxCLIPVisionMBartGenerationMixin:
     # ------------------------------------------------------------------ gen:128-336
     def generate(self, input_ids, max_length: Optional[int] = None, pad_token_id: Optional[int] = None,
@@ -365,16 +380,13 @@ class FlaxCLIPVisionMBartGenerationMixin:
         if not do_sample and num_beams == 1:
             return self._greedy_search(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, procs, lang, sl)
         elif do_sample and num_beams == 1:
-            mcfg = mc
-            top_k = top_k if top_k is not None else getattr(mcfg, "top_k", 50)  # gen:349-356
-            top_p = top_p if top_p is not None else getattr(mcfg, "top_p", 1.0)
-            temperature = temperature if temperature is not None else getattr(mcfg, "temperature", 1.0)
+            warp = dict(top_k=top_k if top_k is not None else getattr(mc, "top_k", 50),  # gen:349-356
+                        top_p=top_p if top_p is not None else getattr(mc, "top_p", 1.0),
+                        temperature=temperature if temperature is not None else getattr(mc, "temperature", 1.0))
             if N > 1:
-                return self._sample_group(ehs, B, N, decoder_start_token_id, max_length, pad_token_id, eos_token_id, prng_key, procs,
-                                          dict(top_k=top_k, top_p=top_p, temperature=temperature), from_processed)
-            return self._sample(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, prng_key, procs,
-                                dict(top_k=top_k, top_p=top_p, temperature=temperature),
-                                from_processed)
+                return self._sample_group(ehs, B, N, decoder_start_token_id, max_length, pad_token_id, eos_token_id, prng_key, procs, warp,
+                                          from_processed)
+            return self._sample(ehs, B, decoder_start_token_id, max_length, pad_token_id, eos_token_id, prng_key, procs, warp, from_processed)
         elif not do_sample and num_beams > 1:
             length_penalty = length_penalty if length_penalty is not None else mc.length_penalty  # gen:733-742
             early_stopping = early_stopping if early_stopping is not None else mc.early_stopping
@@ -384,8 +396,9 @@ class FlaxCLIPVisionMBartGenerationMixin:
             raise NotImplementedError("`Beam sampling is currently not implemented.")  # gen:336
 
     @staticmethod
-    def _proc_args(procs, cur_len: int, max_length: int, eos_token_id: int):
-        """(forced_token, suppress_eos) for this step: MinLength -> ForcedBOS -> ForcedEOS (gen:412-419)."""
+    def _proc_args(procs, cur_len: int, max_length: int, sl=None):
+        """(forced_token, suppress_eos) for this step: MinLength -> ForcedBOS -> ForcedEOS (gen:412-419); forced_token is -1
+        for none and, with the vocabulary shortlist `sl`, the forced id's column in it (what the top-k over its columns counts in)."""
         forced = -1
         # FlaxMinLengthLogitsProcessor: apply_penalty = 1 - clip(cur_len - min_length, 0, 1)  =>  EOS is -inf while cur_len <= min_length
         suppress = procs["min_length"] is not None and cur_len <= procs["min_length"]
@@ -393,9 +406,15 @@ class FlaxCLIPVisionMBartGenerationMixin:
             forced = procs["forced_bos"]
         if procs["forced_eos"] is not None and cur_len == max_length - 1:
             forced = procs["forced_eos"]
-        return forced, suppress
+        return (sl.column(forced) if sl and forced >= 0 else forced), suppress
 
     # ------------------------------------------------------------------ gen:422-535
+    @staticmethod
+    def _plan_key(kind: str, fields: tuple, lang=None, sl=None) -> tuple:
+        """the key of a decode plan: the strategy, what its launch arguments and buffer shapes depend on, then ("G", languages) for a
+        grouped call and ("A", <shortlist key>) for a vocabulary shortlist"""
+        return (kind,) + fields + ((("G", lang["G"]),) if lang else ()) + ((("A",) + sl.key,) if sl else ())
+
     def _decode_plan(self, key, build) -> _DecodePlan:
         """LRU of `_MAX_PLANS` decode plans; `build(plan)` allocates a new plan's tensors."""
         from collections import OrderedDict
@@ -465,6 +484,36 @@ class FlaxCLIPVisionMBartGenerationMixin:
         t[name].view(images, G, beams).copy_(torch.tensor(ids, dtype=torch.int32).to(self.device).view(1, G, 1).expand(images, G, beams))
         return t[name]
 
+    def _start_tokens(self, t, first_col, next_token, start_token, lang, images: int, beams: int):
+        """the start token of every row into `next_token` and into column 0 of the sequences (`first_col`, a view): the scalar
+        start_token, or the language's own for the rows of a grouped call (lang = dict(G, start, bos)).  Returns the per-row
+        ForcedBOS ids of such a call (t["bos_rows"]) or None."""
+        if not lang:
+            first_col.fill_(start_token)  # (a fill kernel: assigning a Python scalar into a device tensor is a synchronous copy)
+            next_token.fill_(start_token)
+            return None
+        next_token.copy_(self._lang_rows(t, lang["start"], images, beams, "start_rows"))
+        first_col.copy_(next_token.view(first_col.shape))
+        return self._lang_rows(t, lang["bos"], images, beams, "bos_rows") if lang["bos"] is not None else None
+
+    def _candidates(self, logits, stat, head, k: int, rows: int, top_val, top_idx, procs, cur_len: int, max_length: int, bos_rows, *,
+                    raw_logits: bool = False, row_bias=None):
+        """the k best continuations of every row after this step's processors, as vocabulary ids (gen:412-419, 850-873).  Greedy: k = 1 on
+        the raw logits; beam search: k = 2K log-probabilities on top of the running scores (row_bias).  head = `_shortlist_of`'s tuple;
+        stat: the head GEMM's per-granule partials where the decoder step returned them."""
+        sl, cols, eos_col, tmap = head
+        forced, suppress = self._proc_args(procs, cur_len, max_length, sl)
+        if bos_rows is not None and cur_len == 1 and forced < 0:  # ForcedBOS per language (a ForcedEOS at max_length == 2 wins)
+            ops.row_forced_topk(rows, k, bos_rows, top_val, top_idx, row_bias=row_bias)
+        elif stat is not None and forced < 0 and k <= 16:
+            # log-softmax + top-k from the head GEMM's per-granule partials: 3908 pairs and a few 64-column granules
+            # per row instead of two passes over the 250 054 logits (same candidates, same order, same fp32 arithmetic)
+            ops.row_topk_tiles(logits, logits.stride(0), cols, stat, k, top_val, top_idx, rows, suppress_eos=suppress, eos_token_id=eos_col,
+                               raw_logits=raw_logits, row_bias=row_bias, token_map=tmap)
+        else:
+            ops.row_lse_topk(logits, logits.stride(0), cols, k, top_val, top_idx, rows, forced_token=forced, suppress_eos=suppress,
+                             eos_token_id=eos_col, raw_logits=raw_logits, row_bias=row_bias, token_map=tmap)
+
     def _greedy_search(self, ehs, B, start_token, max_length, pad_token_id, eos_token_id, procs, lang=None, sl=None):
         """lang = None: B rows.  lang = dict(G, start, bos): G searches per image, row = image * G + g (n_img images below).
         sl: the engine.Shortlist of generate(allowed_token_ids=...) or None"""
@@ -487,103 +536,98 @@ class FlaxCLIPVisionMBartGenerationMixin:
                 t["bos_rows"] = torch.empty(B, dtype=torch.int32, device=dev)
             plan.shortlist = sl
 
-        plan = self._decode_plan(("greedy", B, max_length, pad_token_id, eos_token_id, procs["min_length"], procs["forced_eos"], self.dtype)
-                                 + ((("G", G),) if lang else ()) + ((("A",) + sl.key,) if sl else ()), build)
-        sl, cols, eos_col, tmap = self._shortlist_of(plan, eos_token_id)
+        plan = self._decode_plan(self._plan_key("greedy", (B, max_length, pad_token_id, eos_token_id, procs["min_length"], procs["forced_eos"],
+                                                           self.dtype), lang, sl), build)
+        head = self._shortlist_of(plan, eos_token_id)
         t = plan.t
         sequences, finished, next_token, top_val, top_idx, pos_all = (t[k] for k in ("sequences", "finished", "next_token", "top_val",
                                                                                      "top_idx", "pos_all"))
         sequences.fill_(pad_token_id)  # gen:457
         finished.zero_()
-        bos_rows = None
-        if lang:
-            next_token.copy_(self._lang_rows(t, lang["start"], n_img, 1, "start_rows"))
-            sequences[:, 0].copy_(next_token)
-            if lang["bos"] is not None:
-                bos_rows = self._lang_rows(t, lang["bos"], n_img, 1, "bos_rows")
-        else:
-            sequences[:, 0].fill_(start_token)  # (a fill kernel: assigning a Python scalar into a device tensor is a synchronous copy)
-            next_token.fill_(start_token)
+        bos_rows = self._start_tokens(t, sequences[:, 0], next_token, start_token, lang, n_img, 1)
         cache = self._plan_cache(plan, B, max_length)
         self._decode_set_encoder(cache, ehs.reshape(n_img * st.S, st.d), n_img, G)
-        use_graphs = _graphs_enabled(dev)
 
         def step(cur_len):
-            def fn():
-                with ops.pinned_stream():
-                    cache["cache_index"] = cur_len - 1
-                    logits = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * B: cur_len * B], shortlist=sl)
-                    forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
-                    if sl and forced >= 0:
-                        forced = sl.column(forced)
-                    if bos_rows is not None and cur_len == 1 and forced < 0:  # ForcedBOS per language (a ForcedEOS at max_length == 2 wins)
-                        ops.row_forced_topk(B, 1, bos_rows, top_val, top_idx)
-                    else:
-                        ops.row_lse_topk(logits, logits.stride(0), cols, 1, top_val, top_idx, B, forced_token=forced, suppress_eos=suppress,
-                                         eos_token_id=eos_col, raw_logits=True, token_map=tmap)
-                    ops.greedy_step(B, max_length, cur_len, eos_token_id, pad_token_id, top_idx, 1, sequences, finished, next_token)
-            return fn
+            with ops.pinned_stream():
+                cache["cache_index"] = cur_len - 1
+                logits = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * B: cur_len * B], shortlist=head[0])
+                self._candidates(logits, None, head, 1, B, top_val, top_idx, procs, cur_len, max_length, bos_rows, raw_logits=True)
+                ops.greedy_step(B, max_length, cur_len, eos_token_id, pad_token_id, top_idx, 1, sequences, finished, next_token)
 
-        # gen:480-487 stops when every row has finished.  A finished row only ever receives PAD (gen:501-507) into a buffer that
-        # is PAD already, so steps issued after that point change nothing: the flag is looked at every _POLL steps, not every step.
-        cur_len = 1
-        while cur_len < max_length:
-            if (cur_len - 1) % _POLL == 0 and cur_len > 1 and bool(finished.all().item()):
-                break
-            plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)  # step 1 carries the call's forced-BOS id: never captured
-            cur_len += 1
-        plan.calls += 1
+        _run_chain(plan, step, max_length, lambda: bool(finished.all().item()), _graphs_enabled(dev))  # gen:480-487: every row has finished
         if lang:
             return ModelOutput(sequences=sequences.view(n_img, G, max_length).transpose(0, 1).contiguous())
         return ModelOutput(sequences=sequences.clone())
 
     # ------------------------------------------------------------------ gen:537-663
+    @staticmethod
+    def _warp_in_force(warp, from_processed: bool):
+        """(top_k, top_p, temperature) as the sampling step applies them: 0 / 1.0 / 1.0 where a warper is off, all off in the reference's
+        mode (it draws from the raw logits)"""
+        use_k = from_processed and warp["top_k"] not in (None, 0)
+        use_p = from_processed and warp["top_p"] is not None and warp["top_p"] < 1.0
+        return (warp["top_k"] if use_k else 0, float(warp["top_p"]) if use_p else 1.0,
+                float(warp["temperature"] or 1.0) if from_processed else 1.0)
+
+    def _sample_step_fn(self, t, rows: int, max_length, pad_token_id, eos_token_id, procs, warp, from_processed: bool, draw):
+        """the launches of one sampling step after the decoder's: step(cur_len, logits).  t: the state tensors (sequences, finished,
+        next_token, drawn and — where top-k / top-p are in force — thr, lim); warp: `_warp_in_force`'s triple;
+        draw(cur_len, logits, **kw) launches the categorical draw into t["drawn"], kw being the processed mode's arguments (none in the
+        reference's mode: jax.random.categorical(prng_key, model_outputs.logits[:, -1]), gen:625-627 — no processors)."""
+        top_k, top_p, temp = warp
+        thr, lim = t.get("thr"), t.get("lim")
+
+        def step(cur_len, logits):
+            kw = {}
+            if from_processed:
+                forced, suppress = self._proc_args(procs, cur_len, max_length)
+                if thr is not None and forced < 0:  # gen:338-366: temperature -> top-k -> top-p, as (threshold, tie limit) per row
+                    ops.warp_thresholds(logits, logits.stride(0), self.store.V, thr, lim, rows, temperature=temp, suppress_eos=suppress,
+                                        eos_token_id=eos_token_id, top_k=top_k, top_p=top_p)
+                kw = dict(temperature=temp, forced_token=forced, suppress_eos=suppress, eos_token_id=eos_token_id, min_keep=thr, tie_limit=lim)
+            draw(cur_len, logits, **kw)
+            ops.greedy_step(rows, max_length, cur_len, eos_token_id, pad_token_id, t["drawn"], 1, t["sequences"], t["finished"],
+                            t["next_token"])  # gen:629-642
+        return step
+
     def _sample(self, ehs, B, start_token, max_length, pad_token_id, eos_token_id, prng_key, procs, warp, from_processed: bool):
+        # One draw per image (num_return_sequences None or 1) deliberately keeps its own mechanism: no decode plan, state allocated per
+        # call, the stop test in front of every step, the host-keyed `mic_sample_rows` kernel and no `scores` in the output.  Moving it
+        # onto a plan and `_run_chain` would change the memory held between calls and which kernel the sampling conformance tests
+        # exercise: a behaviour decision, not a tidy-up.  It shares the step body (`_sample_step_fn`) with `_sample_group`.
         from . import prng
         from .modeling_clip_vision_mbart import ModelOutput
 
         dev, st = self.device, self.store
-        use_k = from_processed and warp["top_k"] not in (None, 0)
-        use_p = from_processed and warp["top_p"] is not None and warp["top_p"] < 1.0
-        thr = torch.empty(B, dtype=torch.float32, device=dev) if (use_k or use_p) else None
-        lim = torch.empty(B, dtype=torch.int32, device=dev) if (use_k or use_p) else None
+        warp = self._warp_in_force(warp, from_processed)
+        t = dict(sequences=torch.full((B, max_length), pad_token_id, dtype=torch.int32, device=dev),
+                 finished=torch.zeros(B, dtype=torch.int32, device=dev),
+                 next_token=torch.full((B,), start_token, dtype=torch.int32, device=dev),
+                 drawn=torch.empty((B, 1), dtype=torch.int32, device=dev))
+        if warp[0] or warp[1] < 1.0:
+            t["thr"], t["lim"] = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+        t["sequences"][:, 0].fill_(start_token)  # (a fill kernel: assigning a Python scalar into a device tensor is a synchronous copy)
         key = prng.prng_key(0 if prng_key is None else prng_key)  # gen:561
-        sequences = torch.full((B, max_length), pad_token_id, dtype=torch.int32, device=dev)
-        sequences[:, 0].fill_(start_token)  # (a fill kernel: assigning a Python scalar into a device tensor is a synchronous copy)
-        finished = torch.zeros(B, dtype=torch.int32, device=dev)
-        next_token = torch.full((B,), start_token, dtype=torch.int32, device=dev)
         cache = self.init_cache(B, max_length)
         self._decode_set_encoder(cache, ehs.reshape(B * st.S, st.d), B, 1)
-        drawn = torch.empty((B, 1), dtype=torch.int32, device=dev)
         pos = torch.zeros(B, dtype=torch.int32, device=dev)
-        cur_len = 1
-        while True:
-            if cur_len == max_length or bool(finished.all().item()):  # gen:596-603
+        step = self._sample_step_fn(t, B, max_length, pad_token_id, eos_token_id, procs, warp, from_processed,
+                                    lambda cur_len, logits, **kw: ops.sample_rows(logits, logits.stride(0), st.V, k, t["drawn"], B, **kw))
+        for cur_len in range(1, max_length):
+            if bool(t["finished"].all().item()):  # gen:596-603
                 break
             k, key = prng.split(key)  # gen:610
-            logits = self._decode_step(cache, next_token, pos)
-            if from_processed:
-                forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
-                temp = warp["temperature"] or 1.0
-                if thr is not None and forced < 0:  # gen:338-366: temperature -> top-k -> top-p, as (threshold, tie limit) per row
-                    ops.warp_thresholds(logits, logits.stride(0), st.V, thr, lim, B, temperature=temp, suppress_eos=suppress,
-                                        eos_token_id=eos_token_id, top_k=warp["top_k"] if use_k else 0,
-                                        top_p=warp["top_p"] if use_p else 1.0)
-                ops.sample_rows(logits, logits.stride(0), st.V, k, drawn, B, temperature=temp, forced_token=forced,
-                                suppress_eos=suppress, eos_token_id=eos_token_id, min_keep=thr, tie_limit=lim)
-            else:  # the reference's behaviour: jax.random.categorical(prng_key, model_outputs.logits[:, -1]) (gen:625-627)
-                ops.sample_rows(logits, logits.stride(0), st.V, k, drawn, B)
-            ops.greedy_step(B, max_length, cur_len, eos_token_id, pad_token_id, drawn, 1, sequences, finished, next_token)  # gen:629-642
+            step(cur_len, self._decode_step(cache, t["next_token"], pos))
             pos += 1
-            cur_len += 1
-        return ModelOutput(sequences=sequences)
+        return ModelOutput(sequences=t["sequences"])
 
     def _sample_group(self, ehs, n_img, N, start_token, max_length, pad_token_id, eos_token_id, prng_key, procs, warp, from_processed: bool):
         """generate(do_sample=True, num_return_sequences=N >= 2): N `_sample` calls over the same images — call n with the key
         `split(PRNGKey(prng_key), N)[n]` — as one decode chain of n_img * N rows, row = image * N + n (cross K/V per image: row_div = N).
         mic_sample_rows_keyed gives row (image, n) the noise of row `image` of call n.  Call n alone would stop once ITS rows have all
         finished (gen:596-603); here its rows ride along until every row has: a finished row only ever receives PAD (gen:629-642) into a
-        buffer that is PAD already and leaves its score alone, so that changes nothing (the argument `_greedy_search` relies on).  The
+        buffer that is PAD already and leaves its score alone, so that changes nothing (the argument `_run_chain`'s polling relies on).  The
         per-step keys of all draws are walked on the host before the chain starts and copied into the plan's [max_length][N][2] table:
         the step at cur_len reads its N keys from device memory, a captured step holds the table's address, not a call's keys."""
         from . import prng
@@ -591,9 +635,7 @@ class FlaxCLIPVisionMBartGenerationMixin:
 
         dev, st = self.device, self.store
         R = n_img * N
-        use_k = from_processed and warp["top_k"] not in (None, 0)
-        use_p = from_processed and warp["top_p"] is not None and warp["top_p"] < 1.0
-        temp = float(warp["temperature"] or 1.0) if from_processed else 1.0
+        warp = self._warp_in_force(warp, from_processed)
 
         def build(plan):
             t = plan.t
@@ -604,54 +646,35 @@ class FlaxCLIPVisionMBartGenerationMixin:
             t["scores"] = torch.empty(R, dtype=torch.float32, device=dev)
             t["keys"] = torch.empty((max_length, N, 2), dtype=torch.int32, device=dev)  # the uint32 key words, bit for bit
             t["pos_all"] = torch.arange(max_length, dtype=torch.int32, device=dev).repeat_interleave(R)
-            if use_k or use_p:
+            if warp[0] or warp[1] < 1.0:
                 t["thr"] = torch.empty(R, dtype=torch.float32, device=dev)
                 t["lim"] = torch.empty(R, dtype=torch.int32, device=dev)
 
-        plan = self._decode_plan(("sample", n_img, N, max_length, pad_token_id, eos_token_id,
-                                  (procs["min_length"], procs["forced_bos"], procs["forced_eos"]),
-                                  (warp["top_k"] if use_k else 0, float(warp["top_p"]) if use_p else 1.0, temp), bool(from_processed), self.dtype), build)
+        plan = self._decode_plan(self._plan_key("sample", (n_img, N, max_length, pad_token_id, eos_token_id,
+                                                           (procs["min_length"], procs["forced_bos"], procs["forced_eos"]), warp,
+                                                           bool(from_processed), self.dtype)), build)
         t = plan.t
-        sequences, finished, next_token, drawn, scores, keys, pos_all = (t[k] for k in ("sequences", "finished", "next_token", "drawn", "scores",
-                                                                                        "keys", "pos_all"))
-        thr, lim = t.get("thr"), t.get("lim")
+        sequences, finished, next_token, scores, keys, pos_all = (t[k] for k in ("sequences", "finished", "next_token", "scores", "keys",
+                                                                                 "pos_all"))
         table = prng.step_key_table(prng.split(prng.prng_key(0 if prng_key is None else prng_key), N), max_length)  # gen:561, 610 per draw
         keys.copy_(torch.from_numpy(table.view("int32")))
         sequences.fill_(pad_token_id)
-        sequences[:, 0].fill_(start_token)
-        next_token.fill_(start_token)
+        self._start_tokens(t, sequences[:, 0], next_token, start_token, None, n_img, N)
         finished.zero_()
         scores.zero_()
         cache = self._plan_cache(plan, R, max_length)
         self._decode_set_encoder(cache, ehs.reshape(n_img * st.S, st.d), n_img, N)
-        use_graphs = _graphs_enabled(dev)
+        after_decoder = self._sample_step_fn(
+            t, R, max_length, pad_token_id, eos_token_id, procs, warp, from_processed,
+            lambda cur_len, logits, **kw: ops.sample_rows_keyed(logits, logits.stride(0), st.V, keys[cur_len], t["drawn"], n_img, N,
+                                                                finished=finished, score=scores, **kw))
 
         def step(cur_len):
-            def fn():
-                with ops.pinned_stream():
-                    cache["cache_index"] = cur_len - 1
-                    logits = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R])
-                    kw = dict(finished=finished, score=scores)
-                    if from_processed:
-                        forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
-                        if thr is not None and forced < 0:  # gen:338-366: temperature -> top-k -> top-p, as (threshold, tie limit) per row
-                            ops.warp_thresholds(logits, logits.stride(0), st.V, thr, lim, R, temperature=temp, suppress_eos=suppress,
-                                                eos_token_id=eos_token_id, top_k=warp["top_k"] if use_k else 0,
-                                                top_p=warp["top_p"] if use_p else 1.0)
-                        kw.update(temperature=temp, forced_token=forced, suppress_eos=suppress, eos_token_id=eos_token_id, min_keep=thr,
-                                  tie_limit=lim)
-                    # (the reference's mode: jax.random.categorical(prng_key, model_outputs.logits[:, -1]), gen:625-627 — no processors)
-                    ops.sample_rows_keyed(logits, logits.stride(0), st.V, keys[cur_len], drawn, n_img, N, **kw)
-                    ops.greedy_step(R, max_length, cur_len, eos_token_id, pad_token_id, drawn, 1, sequences, finished, next_token)  # gen:629-642
-            return fn
+            with ops.pinned_stream():
+                cache["cache_index"] = cur_len - 1
+                after_decoder(cur_len, self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R]))
 
-        cur_len = 1
-        while cur_len < max_length:
-            if (cur_len - 1) % _POLL == 0 and cur_len > 1 and bool(finished.all().item()):
-                break
-            plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)  # (step 1 stays eager, as in the other plans)
-            cur_len += 1
-        plan.calls += 1
+        _run_chain(plan, step, max_length, lambda: bool(finished.all().item()), _graphs_enabled(dev))
         return ModelOutput(sequences=sequences.clone(), scores=scores.clone())
 
     # ------------------------------------------------------------------ gen:665-990
@@ -720,24 +743,16 @@ class FlaxCLIPVisionMBartGenerationMixin:
             plan.streams = [torch.cuda.Stream(device=dev) for _ in range(NS)] if NS > 1 else []
             plan.shortlist = sl
 
-        plan = self._decode_plan(("beam", B, K, NS, max_length, pad_token_id, eos_token_id, float(length_penalty), bool(early_stopping),
-                                  procs["min_length"], procs["forced_eos"], self.dtype) + ((("G", G),) if lang else ())
-                                 + ((("A",) + sl.key,) if sl else ()), build)
-        sl = self._shortlist_of(plan, eos_token_id)[0]
+        plan = self._decode_plan(self._plan_key("beam", (B, K, NS, max_length, pad_token_id, eos_token_id, float(length_penalty),
+                                                         bool(early_stopping), procs["min_length"], procs["forced_eos"], self.dtype), lang, sl),
+                                 build)
+        head = self._shortlist_of(plan, eos_token_id)
         ehs = ehs.reshape(n_img, st.S * st.d)
         steps_fn = []
         for i, sub in enumerate(plan.subs):
             t = sub.t
             t["running_seq"].fill_(pad_token_id)  # gen:751-757
-            bos_rows = None
-            if lang:
-                t["next_token"].copy_(self._lang_rows(t, lang["start"], n_img, K, "start_rows"))
-                t["running_seq"][:, :, 0].copy_(t["next_token"].view(Bs, K))
-                if lang["bos"] is not None:
-                    bos_rows = self._lang_rows(t, lang["bos"], n_img, K, "bos_rows")
-            else:
-                t["running_seq"][:, :, 0].fill_(start_token)
-                t["next_token"].fill_(start_token)
+            bos_rows = self._start_tokens(t, t["running_seq"][:, :, 0], t["next_token"], start_token, lang, n_img, K)
             t["seq"].fill_(pad_token_id)
             t["finished"].zero_()  # gen:760
             t["running_scores"].copy_(t["score0"])  # gen:763-765
@@ -753,97 +768,69 @@ class FlaxCLIPVisionMBartGenerationMixin:
                 self._decode_set_encoder(cache, ehs.reshape(n_img * st.S, st.d), n_img, G * K)
             else:
                 self._decode_set_encoder(cache, ehs[i * Bs:(i + 1) * Bs].reshape(Bs * st.S, st.d), Bs, K)
-            # beam_search_cond_fn (gen:798-820) lives on the device: mic_beam_step evaluates it on the new state, and once it says
-            # stop every later mic_beam_step launch is a no-op.  The host therefore enqueues decoder steps (graph replays once the
-            # plan is warm) without waiting and looks at the flag only every _POLL steps.
             t["gstate"].zero_()
             steps_fn.append(self._beam_step_fn(cache, t, Bs, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs,
-                                               groups=G if lang else None, bos_rows=bos_rows, sl=sl))
-        use_graphs = _graphs_enabled(dev, NS)
+                                               head, groups=G if lang else None, bos_rows=bos_rows))
 
         def step(cur_len):
             if NS == 1:
-                return lambda: steps_fn[0](cur_len)
+                return steps_fn[0](cur_len)
+            # fork: every slice's chain on its own stream behind what the current stream has enqueued; join: the current
+            # stream waits for all of them (inside a capture these are the graph's parallel branches)
+            cur = torch.cuda.current_stream()
+            fork = plan.new_event()
+            fork.record(cur)
+            for i, s_ in enumerate(plan.streams):
+                s_.wait_event(fork)
+                with torch.cuda.stream(s_):
+                    steps_fn[i](cur_len)
+                    done = plan.new_event()
+                    done.record(s_)
+                cur.wait_event(done)
 
-            def fn():
-                # fork: every slice's chain on its own stream behind what the current stream has enqueued; join: the current
-                # stream waits for all of them (inside a capture these are the graph's parallel branches)
-                cur = torch.cuda.current_stream()
-                fork = plan.new_event()
-                fork.record(cur)
-                for i, s_ in enumerate(plan.streams):
-                    s_.wait_event(fork)
-                    with torch.cuda.stream(s_):
-                        steps_fn[i](cur_len)
-                        done = plan.new_event()
-                        done.record(s_)
-                    cur.wait_event(done)
-            return fn
-
-        gstates = [sub.t["gstate"] for sub in plan.subs]
-        if lang:
-            # one [G, 8] tensor: a search that has stopped leaves its state alone while its rows ride along (its outputs are those of
-            # the separate call that stopped there); the loop ends when every search has stopped
-            gs = gstates[0]
-            cur_len = 1
-            while cur_len < max_length:
-                plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)
-                cur_len += 1
-                if cur_len < max_length and (cur_len - 1) % _POLL == 0 and bool((gs[:, 3] != 0).all().item()):
-                    break
-            plan.calls += 1
-            t = plan.subs[0].t
-            any_fin = t["finished"].bool().any(dim=1)  # gen:980-990, as below
-            if n_best > 1:
-                out_seq, out_scores = self._n_best(torch.where(any_fin[:, None, None], t["seq"], t["running_seq"]),
-                                                   torch.where(any_fin[:, None], t["scores"], t["running_scores"]), n_best)
-                out = ModelOutput(sequences=out_seq.view(n_img, G, n_best, max_length).transpose(0, 1).reshape(G, n_img * n_best, max_length),
-                                  scores=out_scores.view(n_img, G, n_best).transpose(0, 1).reshape(G, n_img * n_best))
-                out["steps"] = [int(v) for v in gs[:, 4].tolist()]
-                return out
-            out_seq = torch.where(any_fin[:, None, None], t["seq"], t["running_seq"])[:, -1]
-            out_scores = torch.where(any_fin[:, None], t["scores"], t["running_scores"])[:, -1]
-            out = ModelOutput(sequences=out_seq.view(n_img, G, max_length).transpose(0, 1).contiguous(),
-                              scores=out_scores.view(n_img, G).transpose(0, 1).contiguous())
-            out["steps"] = [int(v) for v in gs[:, 4].tolist()]
-            return out
-        cur_len = 1
-        while cur_len < max_length:
-            plan.run_step(cur_len, step(cur_len), use_graphs and cur_len > 1)  # step 1 carries the call's forced-BOS id: never captured
-            cur_len += 1
-            if cur_len < max_length and (cur_len - 1) % _POLL == 0 and all(int(g[3].item()) != 0 for g in gstates):
-                break
-        plan.calls += 1
-        steps = max(int(g[4].item()) for g in gstates)
-        outs = []
-        for sub in plan.subs:
-            t = sub.t
-            any_fin = t["finished"].bool().any(dim=1)  # gen:980
-            out_seq = torch.where(any_fin[:, None, None], t["seq"], t["running_seq"])  # gen:981-983
-            out_scores = torch.where(any_fin[:, None], t["scores"], t["running_scores"])  # gen:984
-            if n_best > 1:
-                out_seq, out_scores = self._n_best(out_seq, out_scores, n_best)
-                outs.append((out_seq.reshape(-1, max_length), out_scores.reshape(-1)))
-                continue
-            outs.append((out_seq[:, -1], out_scores[:, -1]))  # gen:987-990
-        out = ModelOutput(sequences=torch.cat([o[0] for o in outs]).contiguous(), scores=torch.cat([o[1] for o in outs]).contiguous())
-        out["steps"] = steps
+        # the stop flag and step count of every search: word 3 and 4 of a slice's gstate [8], of row g of a grouped call's [G, 8] (a
+        # search that has stopped leaves its state alone while its rows ride along: its outputs are those of the separate call that
+        # stopped there).  The chain ends when every search of every slice has stopped: one host read per slice and poll.
+        gstates = [sub.t["gstate"].view(-1, 8) for sub in plan.subs]
+        _run_chain(plan, step, max_length, lambda: all(bool((g[:, 3] != 0).all().item()) for g in gstates), _graphs_enabled(dev, NS))
+        out = ModelOutput(**self._beam_result([sub.t for sub in plan.subs], n_best, G if lang else None))
+        steps = [g[:, 4].tolist() for g in gstates]
+        out["steps"] = steps[0] if lang else max(s[0] for s in steps)
         return out
+
+    @classmethod
+    def _beam_result(cls, slices, n_best: int, groups=None) -> dict:
+        """gen:980-990 over the state tensors of every slice: an item with a finished hypothesis returns its finished ones, any other
+        its running ones; the n_best best of them, slices concatenated — sequences [items * n_best, max_length], scores
+        [items * n_best], row item * n_best + j.  groups = G (a grouped call, item = image * G + g): [G, images * n_best, max_length]
+        and [G, images * n_best]."""
+        outs = []
+        for t in slices:
+            any_fin = t["finished"].bool().any(dim=1)  # gen:980
+            outs.append(cls._n_best(torch.where(any_fin[:, None, None], t["seq"], t["running_seq"]),  # gen:981-983
+                                    torch.where(any_fin[:, None], t["scores"], t["running_scores"]), n_best))  # gen:984
+        seq, scores = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+        L = seq.shape[-1]
+        if groups is None:
+            return dict(sequences=seq.reshape(-1, L).contiguous(), scores=scores.reshape(-1).contiguous())
+        images = seq.shape[0] // groups
+        return dict(sequences=seq.view(images, groups, n_best, L).transpose(0, 1).reshape(groups, images * n_best, L).contiguous(),
+                    scores=scores.view(images, groups, n_best).transpose(0, 1).reshape(groups, images * n_best).contiguous())
 
     @staticmethod
     def _n_best(out_seq, out_scores, n_best: int):
-        """gen:987-990 at columns K-1, K-2, ..., K-n_best instead of -1: the state is sorted ascending (best last), so the n_best best
-        hypotheses of every item, best first — [items, n_best, max_length] and [items, n_best].  Slots that never held a finished
+        """gen:987-990 at columns K-1, K-2, ..., K-n_best instead of -1 alone: the state is sorted ascending (best last), so the n_best
+        best hypotheses of every item, best first — [items, n_best, max_length] and [items, n_best].  Slots that never held a finished
         hypothesis come back as they lie in the state (PAD rows, score NEG)."""
         return out_seq.flip(1)[:, :n_best].contiguous(), out_scores.flip(1)[:, :n_best].contiguous()
 
-    def _beam_step_fn(self, cache, t, B, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, groups=None,
-                      bos_rows=None, sl=None):
-        """the launches of one beam-search step (gen:822-966) of one slice of B items: step(cur_len).  groups = G: the items belong to G
-        searches (item i to search i % G, gstate [G][8]); bos_rows: per-row ForcedBOS ids of such a call; sl: the call's vocabulary
-        shortlist (the head and the top-k run over its columns, the candidates leave as vocabulary ids: mic_beam_step sees no difference)"""
+    def _beam_step_fn(self, cache, t, B, K, max_length, pad_token_id, eos_token_id, length_penalty, early_stopping, procs, head, groups=None,
+                      bos_rows=None):
+        """the launches of one beam-search step (gen:822-966) of one slice of B items: step(cur_len).  head: `_shortlist_of`'s tuple (with
+        a vocabulary shortlist the head and the top-k run over its columns, the candidates leave as vocabulary ids: mic_beam_step sees
+        no difference); groups = G: the items belong to G searches (item i to search i % G, gstate [G][8]); bos_rows: per-row
+        ForcedBOS ids of such a call"""
         st = self.store
-        cols, eos_col, tmap = (sl.Ns, sl.column(eos_token_id), sl.map) if sl else (st.V, eos_token_id, None)
         R = B * K
         running_seq, seq, finished, running_scores, scores = t["running_seq"], t["seq"], t["finished"], t["running_scores"], t["scores"]
         next_token, src_row, flags, cand_val, cand_idx, pos_all, gstate = (t[k] for k in ("next_token", "src_row", "flags", "cand_val",
@@ -852,20 +839,9 @@ class FlaxCLIPVisionMBartGenerationMixin:
         def step(cur_len):
             with ops.pinned_stream():
                 cache["cache_index"] = cur_len - 1
-                logits, stat = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R], stats=True, shortlist=sl)  # gen:830-840
-                forced, suppress = self._proc_args(procs, cur_len, max_length, eos_token_id)
-                if sl and forced >= 0:
-                    forced = sl.column(forced)
-                if bos_rows is not None and cur_len == 1 and forced < 0:  # ForcedBOS per language (a ForcedEOS at max_length == 2 wins)
-                    ops.row_forced_topk(R, 2 * K, bos_rows, cand_val, cand_idx, row_bias=running_scores.reshape(-1))
-                elif stat is not None and forced < 0 and 2 * K <= 16:
-                    # log-softmax + top-2K from the head GEMM's per-granule partials: 3908 pairs and a few 64-column granules
-                    # per row instead of two passes over the 250 054 logits (same candidates, same order, same fp32 arithmetic)
-                    ops.row_topk_tiles(logits, logits.stride(0), cols, stat, 2 * K, cand_val, cand_idx, R, suppress_eos=suppress,
-                                       eos_token_id=eos_col, row_bias=running_scores.reshape(-1), token_map=tmap)
-                else:
-                    ops.row_lse_topk(logits, logits.stride(0), cols, 2 * K, cand_val, cand_idx, R, forced_token=forced,
-                                     suppress_eos=suppress, eos_token_id=eos_col, row_bias=running_scores.reshape(-1), token_map=tmap)  # gen:850-873
+                logits, stat = self._decode_step(cache, next_token, pos_all[(cur_len - 1) * R: cur_len * R], stats=True, shortlist=head[0])  # gen:830-840
+                self._candidates(logits, stat, head, 2 * K, R, cand_val, cand_idx, procs, cur_len, max_length, bos_rows,
+                                 row_bias=running_scores.reshape(-1))  # gen:850-873
                 ops.beam_step(B, K, max_length, st.V, cur_len, eos_token_id, pad_token_id, length_penalty, early_stopping, cand_val,
                               cand_idx, running_seq, running_scores, seq, scores, finished, src_row, next_token, flags, gstate=gstate,
                               groups=groups)  # gen:872-966
