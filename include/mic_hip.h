@@ -531,7 +531,8 @@ int mic_adamw_clip(int64_t n, float* p, float* m, float* v, const float* g, cons
  *       raw_logits with k = 1 is the greedy argmax: the first maximum of the logits themselves, returned as logit + row_bias
  *       (every other case orders by the fp32 processed value, ties to the lower index).
  *       Like lax.top_k, k > V is refused (so is forced_token >= V) and nothing is written: every index that comes back is < V.
- *   mic_beam_step: the whole bookkeeping of one beam_search_body_fn iteration (gen:857-966) per batch item.
+ *   mic_beam_step: the whole bookkeeping of one beam_search_body_fn iteration (gen:857-966) per batch item.  The divisors
+ *       cur_len ** length_penalty and max_len ** length_penalty are formed on the host, (float)pow(double, (double)length_penalty).
  *   mic_greedy_step: argmax + EOS->PAD substitution + append (gen:499-512).
  * ------------------------------------------------------------------------------------------- */
 int mic_row_lse_topk(int dtype, int R, int V, const void* logits, int ld, int k, int forced_token,

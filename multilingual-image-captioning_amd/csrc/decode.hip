@@ -1,6 +1,8 @@
 // decode.hip — generation epilogues: log-softmax + index-stable top-k over the 250 054-wide head output (K16/K19) and
 // the beam-search bookkeeping of gen:857-966 (K17) as ONE small kernel per step; the KV cache is never gathered
 // (K18) — a [rows][max_len] slot-ownership table is updated instead (see attention.hip / mic_attn_decode).
+#include <cmath>
+
 #include "common.h"
 #include "threefry.h"
 
@@ -445,10 +447,12 @@ extern "C" int mic_row_topk_tiles(int dtype, int R, int V, const void* logits, i
 // ------------------------------------------------------------------ one beam_search_body_fn iteration (gen:857-966)
 // One block per batch item, the (beam, candidate) pairs over its threads: 128 threads up to K = 8 beams (2K*K <= 128 candidates), 512
 // beyond (one pair per thread up to K = 16, four at K = 32).  All arithmetic is fp32 in the reference's operation order so scores are bit-identical to the oracle.
+// The two length-penalty divisors (gen:910, gen:805-807) come from the host as fl32(pow(double)): device powf is an ulp off the
+// correctly rounded value at some (length, penalty) pairs (13 ** 0.5, 9 ** 0.75, 3 ** 1.25, 10 ** 1.2 on gfx950).
 // The items may belong to gridDim.y independent searches (generate() with a sequence of language ids: item i = image * groups + g is
 // item `image` of search g = i % groups; grid = (B / groups, groups), so no block divides; one search: grid = (B, 1)).  A search has
 // its own loop state gs[8] and its own stop test (gen:798-820) over its B / groups items.
-__global__ __launch_bounds__(512) void beam_step_kernel(mic_beam_step_args a) {
+__global__ __launch_bounds__(512) void beam_step_kernel(mic_beam_step_args a, float div_cur, float div_L) {
   extern __shared__ int32_t lds_i[];
   const int K = a.K, C = 2 * K, L = a.max_len, V = a.V;
   const int b = blockIdx.x * gridDim.y + blockIdx.y, tid = threadIdx.x;
@@ -511,7 +515,7 @@ __global__ __launch_bounds__(512) void beam_step_kernel(mic_beam_step_args a) {
     int rank = 0;
     for (int o = 0; o < C; ++o) { const float ov = cand_lp[o]; if (ov > v || (ov == v && o < tid)) ++rank; }
     if (rank < K) { run_pick[K - 1 - rank] = tid; new_run_scores[K - 1 - rank] = v; }
-    float fs = v / powf((float)a.cur_len, a.length_penalty);
+    float fs = v / div_cur;
     const int add_pen = (!cand_fin[tid]) || full;
     fs += (float)add_pen * NEG_BIG;
     fin_score[tid] = fs;
@@ -559,7 +563,7 @@ __global__ __launch_bounds__(512) void beam_step_kernel(mic_beam_step_args a) {
       all_fin &= (nf[kx] != 0);
       mn = fminf(mn, ns[kx]);
     }
-    const float best_running = new_run_scores[K - 1] / powf((float)L, a.length_penalty);
+    const float best_running = new_run_scores[K - 1] / div_L;
     int improve = 1;
     for (int kx = 0; kx < K; ++kx) { const float worst = nf[kx] ? mn : NEG_BIG; improve &= (worst < best_running); }
     a.flags[b * 2 + 0] = all_fin;
@@ -591,7 +595,9 @@ static int beam_step_launch(const mic_beam_step_args* a, int groups, void* strea
   const size_t lds = (size_t)(3 * a->K * a->max_len + 8 * 2 * a->K + 8 * a->K) * 4;
   MIC_CHECK(lds <= 65536, "mic_beam_step: max_len too large for the LDS staging");
   const int threads = 2 * a->K * a->K <= 128 ? 128 : 512;  // one thread per (beam, candidate) pair
-  hipLaunchKernelGGL(beam_step_kernel, dim3(a->B / groups, groups), dim3(threads), lds, (hipStream_t)stream, *a);
+  const float div_cur = (float)std::pow((double)a->cur_len, (double)a->length_penalty);  // cur_len ** length_penalty (gen:910)
+  const float div_L = (float)std::pow((double)a->max_len, (double)a->length_penalty);    // max_length ** length_penalty (gen:805-807)
+  hipLaunchKernelGGL(beam_step_kernel, dim3(a->B / groups, groups), dim3(threads), lds, (hipStream_t)stream, *a, div_cur, div_L);
   MIC_LAUNCH_CHECK();
   return MIC_OK;
 }

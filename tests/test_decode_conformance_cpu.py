@@ -7,7 +7,7 @@
     tests/test_ops_gpu.py / tests/test_generate_gpu.py (random normal logits, atol = 2e-5 max) would have accepted;
   - every decode instantiation of the build's resource table in scope is claimed by a case and launched by the GPU module (its
     committed kernel listing).
-Out of scope (as in the GPU module): mic_beam_step / mic_beam_step_groups."""
+Out of scope (as in the GPU module): mic_beam_step / mic_beam_step_groups — see tests/test_beam_conformance_cpu.py."""
 import fnmatch
 import functools
 import json

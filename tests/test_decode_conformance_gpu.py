@@ -7,8 +7,8 @@ indices distinct and < V; the keep mask of the fp64 warpers; the reference's dra
   - outputs are windows in canary-filled allocations and every element outside the window keeps its bits;
   - logit columns V .. ld, rows past R and stat entries past ntiles hold NaN;
   - each launch runs twice from refilled outputs and gives identical bits (nothing here depends on atomic order for its result).
-Out of scope: mic_beam_step / mic_beam_step_groups (integer logic that test_beam_ids_exact, test_beam_step_groups_* and the oracle
-tie down bit for bit), the _q8 kernels."""
+Out of scope: mic_beam_step / mic_beam_step_groups (their own suite: tests/test_beam_conformance_gpu.py, every search step against
+the oracle's loop body), the _q8 kernels."""
 import functools
 import os
 import sys
