@@ -521,6 +521,21 @@ int mic_grad_sumsq(int64_t n, const float* g, const float* acc, float* partials,
 int mic_clip_coef(const float* partials, int64_t count, float grad_scale, double max_norm, float* out2, void* stream);
 int mic_adamw_clip(int64_t n, float* p, float* m, float* v, const float* g, const float* acc, void* p_lp, const float* hyper,
                    const float* coef, double b1, double b2, double eps, double wd, void* stream);
+/* Parameter groups: optax.multi_transform — one optax.adamw(lr * lr_scale, weight_decay = wd) per group, optax.set_to_zero() for a
+ * frozen one, all with the same b1 / b2 / eps and the same count.  The flat buffer is described once by a table of RUNS in device
+ * memory: sorted, gap-free [begin, end) element ranges of the WHOLE buffer (boundaries multiples of 4 elements; ParamStore's are
+ * multiples of 64), each with its scale, its weight decay and a frozen flag.
+ * mic_adamw_groups: ONE launch updates the flat slice [offset, offset + n) of that buffer; p, m, v, g and p_lp (may be NULL) point
+ *   at the slice's first element, `offset` only places the slice in the table, and the slice may begin and end inside a run and
+ *   cross any number of them.  On every run that is not frozen p, m, v and p_lp are bit for bit those of mic_adamw on that
+ *   sub-range called with hyper[0] replaced by fp32(hyper[0] * lr_scale) (one fp32 multiply) and wd = the run's.  On a frozen run
+ *   nothing is read and nothing is written — master, compute copy and both moments keep their bytes (lr_scale = 0 is NOT frozen:
+ *   the moments move).  Elements of the slice no run covers are left alone.  The table is read by the kernel only: no allocation,
+ *   copy or host wait per call; a caller that knows a slice to be wholly frozen skips the call.  n % 4 == 0, offset % 4 == 0,
+ *   p, m, v, g 16-byte aligned, p_lp 8-byte.  A refused call (MIC_EINVAL) has written nothing. */
+typedef struct { int64_t begin, end; float lr_scale, wd; int32_t frozen, reserved; } mic_adamw_run;  /* 32 bytes */
+int mic_adamw_groups(int64_t n, int64_t offset, float* p, float* m, float* v, const float* g, void* p_lp, const float* hyper,
+                     const mic_adamw_run* runs, int n_runs, double b1, double b2, double eps, float grad_scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Generation epilogues

@@ -81,6 +81,10 @@ class ImageItem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("hwc", C.c_int)]
 
 
+class AdamwRun(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr_scale", C.c_float), ("wd", C.c_float), ("frozen", C.c_int32), ("reserved", C.c_int32)]
+
+
 _i, _f, _p, _u32, _i64 = C.c_int, C.c_float, C.c_void_p, C.c_uint32, C.c_int64
 _SIGS = {
     "mic_version": ([], C.c_int),
@@ -151,6 +155,7 @@ _SIGS = {
     "mic_grad_sumsq": ([_i64, _p, _p, _p, _p], C.c_int),
     "mic_clip_coef": ([_p, _i64, _f, C.c_double, _p, _p], C.c_int),
     "mic_adamw_clip": ([_i64, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, C.c_double, C.c_double, _p], C.c_int),
+    "mic_adamw_groups": ([_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _i, C.c_double, C.c_double, C.c_double, _f, _p], C.c_int),
     "mic_row_lse_topk": ([_i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p], C.c_int),
     "mic_row_lse_topk_mapped": ([_i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p], C.c_int),
     "mic_beam_step": ([C.POINTER(BeamStepArgs), _p], C.c_int),

@@ -100,6 +100,10 @@ class Engine(Fp8Views):
         self.use_head_stats = os.environ.get("MIC_HEAD_STATS", "1") != "0"  # softmax partials out of the LM-head GEMM (A/B switch)
         self.grad_progress = None  # callable(offset): every gradient with flat offset < offset is final (DDP overlap)
         self.on_embed_rows = None  # callable(): single process, right behind the input-embedding scatter at the end of decoder backward
+        # set by Trainer(param_groups=...) for a step in which every segment of the image tower is frozen: loss_and_grads stops at the
+        # bridge (vit_backward_bridge); the gradients of the ViT segments are then NOT computed — their part of ParamStore.grad keeps
+        # whatever it held (the atomic region: the step's zeros)
+        self.skip_vit_backward = False
         # weight-gradient GEMMs on a second stream (bf16 / f32 GEMM modes): nothing but the optimizer depends on dW, so a layer's
         # grouped dW launch runs beside the NEXT layer's dX chain (LayerNorm / attention backward and the small dX GEMMs leave
         # most CUs idle).  The gradient operands dW reads are double-buffered by layer parity; A/B switch MIC_DW_OVERLAP=0|1.
@@ -532,6 +536,13 @@ class Engine(Fp8Views):
         out = torch.empty_like(cls_rows)
         ops.layernorm_fwd(cls_rows, P.f32("vit.post_ln.g"), P.f32("vit.post_ln.b"), self.vit_eps, out, rows=B)
         return out
+
+    def vit_backward_bridge(self, B: int, dehs: torch.Tensor):
+        """the part of vit_backward a frozen image tower still needs: the bridge's weight gradient and bias sum (`vp`), no dX — the
+        ViT's layer backward, its LayerNorm / attention backward, vit_assemble_bwd and the patch-embedding dW do not run"""
+        P = self.P
+        Mv = B * P.S
+        self.linear_bwd("vp", self.buf(f"v{P.vL - 1}.xo", Mv, P.vd), dehs, Mv, dx=None)
 
     def vit_backward(self, B: int, dehs: torch.Tensor):
         P = self.P
@@ -1170,6 +1181,9 @@ class Engine(Fp8Views):
             logits, stat = self.compact_head(hf, M, rows, packed=pack is not None)
             loss = self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=True, stat=stat)
         dehs = self.decoder_backward(B, T, ids, pos_ids, key_mask, ehs, logits, seed, rows=rows, pack=pack)
-        self.vit_backward(B, dehs)
+        if self.skip_vit_backward:
+            self.vit_backward_bridge(B, dehs)
+        else:
+            self.vit_backward(B, dehs)
         self.dw_join()
         return loss

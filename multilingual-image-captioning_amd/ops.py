@@ -550,6 +550,48 @@ def adamw_clip(p, m, v, g, p_lp, hyper, coef, b1, b2, eps, wd, n=None, acc=None)
                                    float(wd), _stream()), "mic_adamw_clip")
 
 
+class AdamwRuns:
+    """The run table of `adamw_groups`: merged runs [(begin, end, lr_scale, wd, frozen)] of a WHOLE flat buffer — sorted, gap-free,
+    boundaries multiples of 4 elements (`train.param_group_table` makes them) — kept twice: on the host, where a wholly frozen slice is
+    recognised without asking the device, and as mic_adamw_run records in device memory, uploaded once here."""
+
+    def __init__(self, runs, device):
+        import numpy as np
+
+        self.runs = [(int(b), int(e), float(s), float(w), bool(f)) for (b, e, s, w, f) in runs]
+        if not self.runs or any(e <= b or b % 4 or e % 4 for (b, e, _, _, _) in self.runs) or any(
+                self.runs[i][1] != self.runs[i + 1][0] for i in range(len(self.runs) - 1)):
+            raise L.MicError("AdamwRuns: runs must be non-empty, sorted and gap-free, with boundaries that are multiples of 4")
+        rec = np.zeros(len(self.runs), dtype=np.dtype([("begin", "<i8"), ("end", "<i8"), ("lr_scale", "<f4"), ("wd", "<f4"),
+                                                       ("frozen", "<i4"), ("reserved", "<i4")]))
+        assert rec.dtype.itemsize == C.sizeof(L.AdamwRun)
+        for i, (b, e, s, w, f) in enumerate(self.runs):
+            rec[i] = (b, e, s, w, int(f), 0)
+        self.dev = torch.from_numpy(rec.view(np.uint8).copy()).to(device)
+        self.begin, self.end = self.runs[0][0], self.runs[-1][1]
+
+    def live(self, offset: int, n: int) -> bool:
+        """does [offset, offset + n) touch a run that is not frozen?"""
+        return any(not f and b < offset + n and e > offset for (b, e, _, _, f) in self.runs)
+
+
+def adamw_groups(table: AdamwRuns, offset, p, m, v, g, p_lp, hyper, b1, b2, eps, grad_scale=1.0, n=None):
+    """AdamW with parameter groups on flat slice [offset, offset + n) of the buffer `table` describes (mic_adamw_groups): p, m, v, g,
+    p_lp are the SLICE's tensors.  One launch, whatever number of runs the slice crosses; none when the slice is wholly frozen
+    (returns False).  Per call: no allocation, no copy, no host wait."""
+    n = int(n if n is not None else p.numel())
+    offset = int(offset)
+    if offset < table.begin or offset + n > table.end:
+        raise L.MicError(f"adamw_groups: slice [{offset}, {offset + n}) lies outside the table's [{table.begin}, {table.end})")
+    if min(p.numel(), m.numel(), v.numel(), g.numel(), n if p_lp is None else p_lp.numel()) < n:
+        raise L.MicError("adamw_groups: a tensor is shorter than the slice")
+    if not table.live(offset, n):
+        return False
+    L.check(L.lib().mic_adamw_groups(n, offset, _p(p), _p(m), _p(v), _p(g), _p(p_lp), _p(hyper), _p(table.dev), len(table.runs), float(b1),
+                                     float(b2), float(eps), float(grad_scale), _stream()), "mic_adamw_groups")
+    return True
+
+
 def row_flags(ids, n_ids, flags):
     """flags[:] = 0; flags[ids[i]] = 1 for i < n_ids (uint8 flags, int32 ids)"""
     L.check(L.lib().mic_row_flags(_p(ids), int(n_ids), _p(flags), flags.numel(), _stream()), "mic_row_flags")

@@ -484,6 +484,90 @@ def virtual_rank_dropout_seed(seed: int, rank: int, step: int, accumulate_steps:
     return (stream + int(step) * 0x9E3779B1) & 0xFFFFFFFF
 
 
+# ---- parameter groups (Trainer(param_groups=...)): ready-made matchers over the ParamStore segment names, applied with re.fullmatch
+ENCODER = r"vit.*|patch\.w"   # the image tower: every vit* segment and the patch embedding; the bridge vp.* is not part of it
+NO_DECAY = r".*\.[bg]|flb"    # biases and LayerNorm scales / biases (HF's decay mask); the embeddings (shared, dec.pos, vit.pos, vit.cls) decay
+_GROUP_KEYS = ("match", "lr_scale", "weight_decay", "frozen")
+
+
+def _check_param_groups(param_groups) -> None:
+    """the part of the validation that needs no store: shape of the argument, keys, value ranges (ValueError)"""
+    import math
+    import numbers
+
+    if not isinstance(param_groups, list) or not all(isinstance(g, dict) for g in param_groups):
+        raise ValueError(f"param_groups must be None or a list of dicts, got {type(param_groups).__name__}")
+    for i, g in enumerate(param_groups):
+        unknown = sorted(set(g) - set(_GROUP_KEYS), key=str)
+        if unknown:
+            raise ValueError(f"param_groups[{i}]: unknown key(s) {unknown}; known: {list(_GROUP_KEYS)}")
+        if "match" not in g:
+            raise ValueError(f"param_groups[{i}]: 'match' is missing")
+        mt = g["match"]
+        if not (isinstance(mt, str) or callable(mt) or (isinstance(mt, (list, tuple)) and mt and all(isinstance(x, str) for x in mt))):
+            raise ValueError(f"param_groups[{i}]: 'match' must be a regex string, a non-empty list of regex strings or a callable, got {mt!r}")
+        for key, low in (("lr_scale", 0.0), ("weight_decay", None)):
+            if key in g:
+                x = g[key]
+                if (isinstance(x, (bool, np.bool_)) or not isinstance(x, numbers.Real) or not math.isfinite(x)
+                        or (low is not None and x < low)):
+                    raise ValueError(f"param_groups[{i}]: {key} must be a finite real number{' >= 0' if low is not None else ''}, got {x!r}")
+        if "frozen" in g and not isinstance(g["frozen"], (bool, np.bool_)):
+            raise ValueError(f"param_groups[{i}]: frozen must be a bool, got {g['frozen']!r}")
+
+
+def _segment_groups(store, param_groups, weight_decay: float) -> List[Tuple[str, int, float, float, bool]]:
+    """[(segment, offset, lr_scale, wd, frozen)] in flat order: the first matching group wins, an unmatched segment keeps
+    (1, weight_decay, False).  ValueError for a malformed argument and for a group that matches no segment."""
+    import re
+
+    _check_param_groups(param_groups)
+
+    def matcher(mt):
+        if callable(mt):
+            return lambda name: bool(mt(name))
+        pats = [re.compile(x) for x in ([mt] if isinstance(mt, str) else mt)]
+        return lambda name: any(p.fullmatch(name) for p in pats)
+
+    fns = [matcher(g["match"]) for g in param_groups]
+    hits = [0] * len(fns)
+    out = []
+    for s in sorted(store.segs.values(), key=lambda s: s.offset):
+        lr_scale, wd, frozen = 1.0, float(weight_decay), False
+        first = True
+        for i, (fn, g) in enumerate(zip(fns, param_groups)):
+            if fn(s.name):
+                hits[i] += 1  # (a group shadowed everywhere by earlier ones still names real segments: not an error)
+                if first:
+                    lr_scale, wd, frozen = float(g.get("lr_scale", 1.0)), float(g.get("weight_decay", weight_decay)), bool(g.get("frozen", False))
+                    first = False
+        out.append((s.name, s.offset, lr_scale, wd, frozen))
+    for i, h in enumerate(hits):
+        if h == 0:
+            raise ValueError(f"param_groups[{i}]: match {param_groups[i]['match']!r} matches no parameter segment "
+                             f"(names look like {', '.join(list(store.segs)[:3])}, ..., vit0.ln1.g, vp.w)")
+    return out
+
+
+def param_group_table(store, param_groups, weight_decay: float = 0.0) -> List[Tuple[int, int, float, float, bool]]:
+    """Merged runs [(begin, end, lr_scale, wd, frozen)] of the flat parameter buffer under `param_groups` (Trainer's argument): they
+    cover [0, store.numel) without gaps, in order; a segment's alignment padding goes with the segment in front of it, adjacent runs
+    with equal settings are one run, boundaries are multiples of ParamStore's alignment (64 elements).  A frozen run reports
+    lr_scale = wd = 0 — nothing of a frozen group's settings is ever used — so neighbouring frozen groups merge.  Host only: a
+    `ParamStore(allocate=False)` is enough."""
+    segs = _segment_groups(store, param_groups, weight_decay)
+    runs: List[Tuple[int, int, float, float, bool]] = []
+    for k, (_, off, lr_scale, wd, frozen) in enumerate(segs):
+        begin = 0 if k == 0 else off
+        end = segs[k + 1][1] if k + 1 < len(segs) else store.numel
+        key = (0.0, 0.0, True) if frozen else (lr_scale, wd, False)
+        if runs and runs[-1][2:] == key:
+            runs[-1] = (runs[-1][0], end) + key
+        else:
+            runs.append((begin, end) + key)
+    return runs
+
+
 class Trainer:
     """TrainState + train_step/eval_step of main.py, for one rank.
 
@@ -507,13 +591,31 @@ class Trainer:
     in fp32, partials added in fp64); AdamW can no longer start before the last gradient exists, so it leaves the buckets: one pass
     over the whole buffer behind backward that reads the coefficient from device memory — the host never waits for the norm.  Every
     `train_step` call that takes the optimizer step additionally returns "grad_norm", the pre-clip norm as a fresh device scalar
-    (identical on all ranks by construction); `c = math.inf` measures without clipping."""
+    (identical on all ranks by construction); `c = math.inf` measures without clipping.
+
+    Parameter groups (`param_groups=[dict(match=..., lr_scale=1.0, weight_decay=<the Trainer's>, frozen=False), ...]`):
+    `optax.multi_transform` — one `optax.adamw(lr_fn * lr_scale, weight_decay=wd)` per group with the Trainer's b1 / b2 / eps and the
+    global count, `optax.set_to_zero()` for a frozen group.  The reference builds one `optax.adamw` over all leaves (main.py:629-635),
+    so this is opt-in and `None` leaves the step what it is, launch for launch.  `match` is a regex string, a list of them or a
+    callable over the ParamStore segment names (`vit3.qkv.w`, `dec0.ln_sa.g`, `shared`, `flb`, `vp.w`, ...), regexes applied with
+    `re.fullmatch`; the first matching group wins, an unmatched segment keeps the Trainer's weight decay and scale 1; `ENCODER` and
+    `NO_DECAY` are ready-made matchers.  A leaf that is not frozen takes the usual element update with lr = fp32(lr * lr_scale) and
+    its group's wd; of a frozen leaf no byte of master, compute copy, m or v ever changes (lr_scale = 0 is not frozen: the moments
+    move).  The returned "learning_rate" stays the base rate; checkpoints are unchanged.  The groups reach the optimizer as a table
+    of merged runs (`param_group_table`) uploaded once; every optimizer pass is one `mic_adamw_groups` launch over its slice, and a
+    wholly frozen slice launches nothing.  The row split of the tied embedding is off (as with clipping: its pieces wait for the end
+    of backward).  With several ranks the exchange is untouched: buckets inside frozen ranges travel as they lie and are ignored.
+    When every segment of `ENCODER` is frozen, backward stops at the bridge (`skip_frozen_backward=True`, the default): the ViT's
+    layer backward, its weight-gradient GEMMs and the patch-embedding gradient do not run, and the gradient buffer of those segments
+    holds nothing meaningful after the step.  Not combined with gemm_dtype="fp8", accumulate_steps > 1, max_grad_norm or
+    emulate_comm."""
 
     def __init__(self, model, learning_rate_fn: Callable[[int], float], b1=0.9, b2=0.999, eps=1e-8, weight_decay=0.0,
                  label_smoothing_factor=0.0, seed: int = 42, bucket_mb: float = 64.0, group=None, compact_head: bool = True,
                  overlap_optimizer: bool = True, grad_comm_dtype=None, gemm_dtype: Optional[str] = None,
                  fp8_scaling: str = "delayed", pack_rows: bool = True, comm_cus: Optional[int] = None, emulate_comm: int = 0,
-                 fp8_head: Optional[str] = None, accumulate_steps: int = 1, max_grad_norm: Optional[float] = None):
+                 fp8_head: Optional[str] = None, accumulate_steps: int = 1, max_grad_norm: Optional[float] = None,
+                 param_groups: Optional[List[Dict]] = None, skip_frozen_backward: bool = True):
         """pack_rows (bfloat16 mode, with compact_head): the decoder runs on the valid caption positions only (`packed_rows`);
         exact — padded positions neither carry loss nor are attended to — and ~1/3 fewer decoder rows on ragged captions at seq 64,
         nearly half at seq 128.  Any seq_len up to max_position_embeddings and any number of encoder positions: beyond one 64x64
@@ -534,12 +636,30 @@ class Trainer:
         scales and the weight re-quantisation inside the optimizer passes assume one pass per step) or with emulate_comm.
         max_grad_norm = c (a real number > 0, math.inf allowed; default None = off, the reference's step): global-norm clipping
         in front of AdamW (class docstring).  c = inf measures the norm without clipping.  Not combined with gemm_dtype="fp8" (the
-        two-phase refresh of the fp8 weight copies keys on per-bucket optimizer progress) or with emulate_comm."""
+        two-phase refresh of the fp8 weight copies keys on per-bucket optimizer progress) or with emulate_comm.
+        param_groups (default None = one AdamW over all leaves, the reference's step): per-group learning-rate scale, weight decay
+        and freezing (class docstring).  skip_frozen_backward (with param_groups only): True = a frozen image tower's backward does
+        not run; False keeps the full backward (its gradients are computed and ignored)."""
         import math
         import numbers
 
         import torch.distributed as dist
 
+        if param_groups is not None:
+            # everything here comes before the model is touched: the argument's shape, then the combinations that are out of scope
+            _check_param_groups(param_groups)
+            if gemm_dtype == "fp8":
+                raise ValueError("param_groups is not supported together with gemm_dtype='fp8' (out of scope: the refresh of the fp8 weight "
+                                 "copies inside the optimizer passes knows nothing of frozen ranges)")
+            if not isinstance(accumulate_steps, (bool, np.bool_)) and isinstance(accumulate_steps, (int, np.integer)) and accumulate_steps > 1:
+                raise ValueError("param_groups is not supported together with accumulate_steps > 1 (out of scope: AdamW on g + acc has "
+                                 "no grouped form)")
+            if max_grad_norm is not None:
+                raise ValueError("param_groups is not supported together with max_grad_norm (out of scope: the clipped AdamW pass has no "
+                                 "grouped form, and the norm of a partly frozen gradient needs its own definition)")
+            if emulate_comm:
+                raise ValueError("param_groups is not supported together with emulate_comm (out of scope: the stand-in exchange models "
+                                 "the step whose optimizer passes all run)")
         if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer)) or accumulate_steps < 1:
             raise ValueError(f"accumulate_steps must be an integer >= 1, got {accumulate_steps!r}")
         if max_grad_norm is not None:
@@ -573,6 +693,21 @@ class Trainer:
         self.group = group
         self.seed = seed
         st = model.store
+        # parameter groups, host side (before any device work): which group every segment belongs to, the merged runs, and whether
+        # the image tower is frozen as a whole
+        self._group_runs = self._groups = None
+        self._encoder_frozen = False
+        if param_groups is not None:
+            if getattr(model.engine, "fp8", False):
+                raise ValueError("param_groups is not supported together with gemm_dtype='fp8' (out of scope: the refresh of the fp8 weight "
+                                 "copies inside the optimizer passes knows nothing of frozen ranges)")
+            import re
+
+            per_seg = _segment_groups(st, param_groups, weight_decay)
+            self._group_runs = param_group_table(st, param_groups, weight_decay)
+            enc = [frozen for (name, _, _, _, frozen) in per_seg if re.fullmatch(ENCODER, name)]
+            self._encoder_frozen = bool(enc) and all(enc)
+        self.skip_frozen_backward = bool(skip_frozen_backward)
         st.ensure_grads()
         st.ensure_opt_state()
         if gemm_dtype is not None:
@@ -629,13 +764,21 @@ class Trainer:
         # stream's mask.
         # Clipping (max_grad_norm): AdamW cannot start before the last gradient exists, so the optimizer leaves the buckets — the row
         # split only serves the early passes and is off; what runs per bucket beside backward is the bucket's sum of squares.
+        # Parameter groups: the row split is off as well — there are no group-aware row passes; the pieces of the tied embedding wait for
+        # the end of backward, every other bucket's grouped pass still runs beside it.
         clip = self.max_grad_norm is not None
-        self._split_shared = (self.overlap_optimizer and model.device.type == "cuda" and not clip
+        grouped = self._group_runs is not None
+        self._split_shared = (self.overlap_optimizer and model.device.type == "cuda" and not clip and not grouped
                               and _os.environ.get("MIC_OPT_SPLIT_SHARED", "1") != "0" and sh.numel % st.d == 0)
         self._sh = (sh.offset, sh.offset + sh.numel, st.d)
         self._row_flag = torch.zeros(sh.numel // st.d, dtype=torch.uint8, device=model.device) if self._split_shared else None
         opt_cus = (int(_os.environ.get("MIC_OPT_CUS", str(OPT_CUS_DEFAULT)))
-                   if (model.device.type == "cuda" and (self._split_shared or (clip and self.overlap_optimizer))) else 0)
+                   if (model.device.type == "cuda" and (self._split_shared or ((clip or grouped) and self.overlap_optimizer))) else 0)
+        # (tools/param_groups_probe.py switches a live Trainer between the grouped forms and the plain step by writing `_groups`,
+        # `_group_runs`, `_encoder_frozen`, `skip_frozen_backward`, `_split_shared`, `_row_flag` and the reducer's `ready_when`: state
+        # derived from param_groups beyond those has to be added to its `mode()` too)
+        if grouped:
+            self._groups = ops.AdamwRuns(self._group_runs, model.device)  # the device table: made once, read by every grouped pass
         import weakref
 
         me = weakref.ref(self)  # the reducer's callbacks must not own the Trainer (Trainer -> reducer -> bound method -> Trainer is a cycle
@@ -706,6 +849,10 @@ class Trainer:
         slice inside the tied embedding (whole rows: the bucket cuts inside that segment are row-aligned) skips the rows flagged
         for this step when the row split is on (`_adamw_shared_late` takes those)."""
         st = self.model.store
+        if self._groups is not None:  # parameter groups: one launch whatever runs the slice crosses, none if all of them are frozen
+            ops.adamw_groups(self._groups, b, st.master[b:e], st.m[b:e], st.v[b:e], st.grad[b:e], None if st.lp is st.master else st.lp[b:e],
+                             self.hyper, self.b1, self.b2, self.eps, grad_scale=self._gscale, n=e - b)
+            return
         sb, se, width = self._sh
         lo, hi = max(b, sb), min(e, se)
         if not self._split_shared or lo >= hi:
@@ -906,6 +1053,8 @@ class Trainer:
         eng.grad_progress = r.progress if r.active else None
         # the sparse input-embedding rows: scattered locally while accumulating (acc carries them), exchanged on the last micro-step
         eng.defer_embed = final and self.world > 1
+        # a frozen image tower: backward stops at the bridge (Engine.loss_and_grads)
+        eng.skip_vit_backward = self._encoder_frozen and self.skip_frozen_backward
         # single process: the flagged rows of the tied embedding get their optimizer pass as soon as decoder backward has scattered the
         # input-embedding rows into them — under the ViT's backward instead of behind the step (0.09 ms + a stream hand-over)
         self._late_done = False
@@ -937,6 +1086,8 @@ class Trainer:
                      after=self._adamw_shared_late if (self._split_shared and not self._late_done) else None)
             if self._clip_out is not None:
                 self._clipped_adamw(per_bucket)
+            elif not self.overlap_optimizer and self._groups is not None:
+                self._adamw_slice(0, st.numel)
             elif not self.overlap_optimizer:
                 ops.adamw(st.master, st.m, st.v, st.grad, None if st.lp is st.master else st.lp, self.hyper, self.b1, self.b2, self.eps,
                           self.wd, grad_scale=self._gscale, acc=st.acc if self._use_acc else None)
@@ -955,6 +1106,7 @@ class Trainer:
                 eng.f8.weights_changed()
             raise
         finally:
+            eng.skip_vit_backward = False
             eng.on_embed_rows, eng.grad_progress, self._use_acc = None, None, False  # (whatever happened: no hooks into this Trainer stay behind)
         self.step += 1
         self._micro = 0
