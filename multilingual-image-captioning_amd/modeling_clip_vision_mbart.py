@@ -390,7 +390,14 @@ class FlaxCLIPVisionMBartForConditionalGeneration(FlaxCLIPVisionMBartPreTrainedM
         if fold:
             # (sum, sum of squares) per row of x (layer input; layer 0's comes from an explicit LayerNorm), x1, x2 — zeroed once per step
             lnst = eng.buf(ns + "g.lnstats", st.L * 3 * R, 2, torch.int64)[: st.L * 3 * R].view(st.L, 3, R, 2)  # 2^20 fixed point
-            ops.zero(lnst)
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                # while a decode plan captures the step: a fill KERNEL, not ops.zero's hipMemsetAsync — as a memset node of the hipGraph
+                # it is not ordered against the atomics of the step's GEMMs on replay: the statistics of a replayed step varied from
+                # call to call and with them the tokens (tests/test_coherence_gpu.py: a warm bf16 plan against a twin).  The step's
+                # launches are pinned to torch's current stream (ops.pinned_stream), so this one runs in line with them
+                lnst.zero_()
+            else:
+                ops.zero(lnst)
         eps = eng.dec_eps
         for l in range(st.L):
             p = f"dec{l}."

@@ -1100,10 +1100,11 @@ class Trainer:
                 # stream of its own — it has the whole next forward pass to finish (engine.shared_T waits for it)
                 eng.refresh_shared_T(aux, st.version)
         except BaseException:
-            # a step that raised: some optimizer passes may have run, a refresh of the fp8 weight copies may be under way — the next pass
-            # waits for it and re-makes them all from the weights as they are, their scale history restarted (Fp8State)
-            if eng.f8 is not None:
-                eng.f8.weights_changed()
+            # a step that raised: some optimizer passes may have run — master and compute copy have moved, so everything derived from them
+            # (model.params, E^T, the LayerNorm folds, vocabulary shortlists: ParamStore.version) is stale; a refresh of the fp8 weight
+            # copies may be under way — the next pass waits for it and re-makes them all from the weights as they are, their scale
+            # history restarted (Fp8State)
+            m.invalidate_params_cache()
             raise
         finally:
             eng.skip_vit_backward = False

@@ -243,6 +243,27 @@ def test_decode_layernorm_fold_matches_explicit_layernorms(dev):
     v0 = model.store.version
     model.invalidate_params_cache()
     assert model.store.version == v0 + 1
+    # ... with their values: after the weights really change, the folded steps' logits are those of a twin holding the new weights
+    from mic_amd.params import flatten_tree, unflatten_tree
+
+    def folded_logits(m):
+        e = m.encode(px.numpy())
+        c = m.init_cache(B, L, e)
+        out = []
+        for t in range(3):
+            o = m.decode(toks[t], e, decoder_position_ids=np.full((B, 1), t, dtype=np.int32), past_key_values=c)
+            c = o.past_key_values
+            out.append(torch.as_tensor(o.logits).clone())
+        return torch.stack(out)
+
+    old = folded_logits(model)
+    assert torch.equal(old.float().cpu().reshape(3, B, -1), a[:3])  # (the folds in use are the ones compared above)
+    new = unflatten_tree({k: np.asarray(v, np.float32) * np.float32(1.25) + np.float32(0.01) for k, v in flatten_tree(model.params).items()})
+    model.params = new
+    _, _, twin = make_pair(torch.bfloat16, dev, gelu="tanh", decoder_ln_eps=1e-6, d_layers=3)
+    twin.params = new
+    got = folded_logits(model)
+    assert twin.engine.decode_ln_fold and torch.equal(got, folded_logits(twin)) and not torch.equal(got, old)
 
 
 def _rule_batch(rc, classes, T=12, n=8):
