@@ -209,6 +209,17 @@ class Engine(Fp8Views):
 
     # ------------------------------------------------------------------ buffers
     def buf(self, name: str, rows: int, cols: int, dtype=None) -> torch.Tensor:
+        """The buffer `name` of capacity `rows` x `cols`: zeros on first touch, the SAME tensor (whatever the last call left in it) ever
+        after.  The buffer contract (table and tests: tests/util_poison.py, tests/test_poison_gpu.py):
+        SCRATCH — rows [0, rows): a caller writes what it reads, in every call, and bounds its reads by the call's valid rows; nothing
+          may depend on the previous contents.  That is every buffer handed out here and by `vec` except the STATE ones below; the
+          decoder step's `g.ehs` / `g.ckv<l>` are the sequence's state between the steps of one `decode()` sequence.
+        REST — rows [rows, allocation) (the padding to 128 rows): zero for ever, no kernel may write them — the fp32 weight-gradient
+          GEMMs and the patch-embedding dW reduce over the padded row count.  (Elsewhere: unused `Fp8State` slots and a shortlist's
+          padding are zero; the workspace of mic_embed_rows_add_det is owner = INT_MAX, count = 0, last = -1, multi_count = 0.)
+        STATE — `w.sharedT` (E^T, a derived weight copy: `shared_T`) and `ones_i32` (built once, only grows).  (Elsewhere: weights,
+          AdamW moments, `acc`, the Trainer's `hyper`, the fp8 scale history and weight copies, LayerNorm folds, shortlists, a decode
+          plan's constants.)"""
         dtype = dtype or self.dt
         key = (name, rows, cols, dtype)  # (a tuple: this lookup runs ~1500 times per train step on the host)
         t = self._bufs.get(key)
