@@ -308,6 +308,25 @@ int mic_attn_bwd_packed_tiled(int dtype, int B, int H, int Tq_max, int Tk, const
                               const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
                               const void* dout, int lddo, const float* lse, int causal, void* dq, int lddq, void* dk, int lddk,
                               void* dv, int lddv, void* stream);
+/* One-tile cross-attention with keys / values SHARED by G query sequences (training on several captions per image: the image tower
+ * and the cross k/v projections run once per image).  B = n_img * G query sequences, image-major: sequence b attends the dense key /
+ * value rows [(b / G)*Tk, (b / G + 1)*Tk).  Its own rows are [b*Tq_max, (b+1)*Tq_max) when q_off == NULL (dense rows), otherwise
+ * [q_off[b], q_off[b] + q_len[b]) (packed rows; q_off and q_len go together).  No key mask and no causal flag.  lse [B][H][Tq_max] in
+ * the one-tile layout.  Tq_max <= 64, Tk <= 64, head width 64, MIC_BF16 / MIC_F32, row strides under the alignment rules of
+ * mic_attn_fwd_packed; a refused call (MIC_EINVAL) writes nothing, and in packed form nothing behind q_len[b] is written.
+ * fwd: one workgroup per (caption, head); out and lse are bit for bit those of mic_attn_fwd / mic_attn_fwd_packed (kv_packed = 0) on
+ * K / V rows replicated G times.
+ * bwd: one workgroup per (image, head) stages K and V once and walks its G captions in ascending order; dq is bit for bit the one-tile
+ * kernels' on replicated K / V; dk / dv [n_img*Tk rows] are the sums over an image's captions, held in fp32 accumulators over the whole
+ * walk and stored once (one rounding in bf16; no atomics, no scratch matrix: the same bytes give the same bits).  G == 1: all five
+ * outputs are bit for bit those of the existing one-tile kernels. */
+int mic_attn_fwd_shared(int dtype, int n_img, int G, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len,
+                        const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse,
+                        void* stream);
+int mic_attn_bwd_shared(int dtype, int n_img, int G, int H, int Tq_max, int Tk, const int32_t* q_off, const int32_t* q_len,
+                        const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* out, int ldo,
+                        const void* dout, int lddo, const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv,
+                        void* stream);
 /* mic_attn_bwd / mic_attn_bwd_packed (q_off == NULL: dense rows) of the bf16 single-tile kernel with dQ / dK / dV written as fp8
  * bytes under delayed scaling (mic_fp8_out): dq8 describes dQ's byte matrix and tensor, dk8 dK's; dV (dv8) shares dK's leading
  * dimension, scale and amax table — dK and dV are the two halves of ONE [rows][2d] (or, with dQ, [rows][3d]) gradient tensor. */

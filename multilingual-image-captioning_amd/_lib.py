@@ -116,6 +116,8 @@ _SIGS = {
     "mic_attn_fwd_packed": ([_i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _p, _p], C.c_int),
     "mic_attn_fwd_packed_tiled": ([_i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _p, _p], C.c_int),
     "mic_attn_bwd_packed": ([_i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p], C.c_int),
+    "mic_attn_fwd_shared": ([_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p], C.c_int),
+    "mic_attn_bwd_shared": ([_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p], C.c_int),
     "mic_attn_bwd_packed_tiled": ([_i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p], C.c_int),
     "mic_attn_decode": ([_i, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p], C.c_int),
     "mic_kv_append": ([_i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p], C.c_int),

@@ -111,6 +111,9 @@ class Engine(Fp8Views):
         # decoder-step LayerNorms folded around the GEMMs (bfloat16 generate path): A/B switch
         self.decode_ln_fold = self.dev.type == "cuda" and os.environ.get("MIC_DECODE_LNFOLD", "1") != "0"
         self._ckv_hoist = os.environ.get("MIC_CKV_HOIST", "1") != "0"
+        # several captions per image (kv_group > 1), one-tile sizes: the shared-K/V kernels, or MIC_ATTN_SHARED=tiled: an image's
+        # captions as one sequence of the existing cores (A/B; beyond one tile that is the only form)
+        self.attn_shared_tiled = os.environ.get("MIC_ATTN_SHARED", "") == "tiled"
         self._lnf = {}
         self._lnf_version = -1
         self._dw_stream = None
@@ -247,21 +250,55 @@ class Engine(Fp8Views):
         self._lnf_version = -1
 
     # ------------------------------------------------------------------ attention cores: which entry point takes a call
-    def attn_forward(self, q, k, v, out, lse, B, H, Tq, Tk, *, ldq, ldk, ldv, ldo, pack=None, kv_packed=False, key_mask=None, causal=False):
+    def attn_forward(self, q, k, v, out, lse, B, H, Tq, Tk, *, ldq, ldk, ldv, ldo, pack=None, kv_packed=False, key_mask=None, causal=False,
+                     kv_group=1):
         """out, lse = attention of q over k / v.  pack = (q_off, q_len, rows) or None: packed query rows take the packed cores (one-tile
         or tiled by `packed_attn_tiled`), which know no key mask — every position of a packed sequence is valid; kv_packed: the keys
-        are those packed rows too (self-attention), not [B][Tk] rows (cross-attention)."""
-        if pack is None:
+        are those packed rows too (self-attention), not [B][Tk] rows (cross-attention).
+        kv_group = G > 1 (cross-attention only: no mask, not causal, not kv_packed): the B = n_img * G query sequences are image-major
+        and sequence b attends the Tk rows of image b // G.  One tile: the shared-K/V kernels.  Beyond one tile (or MIC_ATTN_SHARED=tiled)
+        an image's G consecutive captions are ONE sequence of the existing cores — cross-attention couples no two queries — dense rows
+        as B' = n_img, Tq' = G*Tq, packed rows through the grouped description pack[3:5] (`train.group_packed_rows`)."""
+        if kv_group > 1:
+            n_img, G = self._kv_group_call(B, kv_group, kv_packed, key_mask, causal)
+            if not (packed_attn_tiled(Tq, Tk) or self.attn_shared_tiled):
+                q_off, q_len = (None, None) if pack is None else pack[:2]
+                ops.attn_fwd_shared(q, k, v, out, n_img, G, H, Tq, Tk, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, q_off=q_off, q_len=q_len, lse=lse)
+            elif pack is None:
+                ops.attn_fwd(q, k, v, out, n_img, H, G * Tq, Tk, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, lse=lse)
+            else:
+                ops.attn_fwd_packed_tiled(q, k, v, out, n_img, H, G * Tq, Tk, pack[3], pack[4], kv_packed=False, ldq=ldq, ldk=ldk, ldv=ldv,
+                                          ldo=ldo, lse=lse)
+        elif pack is None:
             ops.attn_fwd(q, k, v, out, B, H, Tq, Tk, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, key_mask=key_mask, causal=causal, lse=lse)
         else:
             fwd = ops.attn_fwd_packed_tiled if packed_attn_tiled(Tq, Tk) else ops.attn_fwd_packed
             fwd(q, k, v, out, B, H, Tq, Tk, pack[0], pack[1], kv_packed=kv_packed, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, causal=causal, lse=lse)
 
+    def _kv_group_call(self, B, G, kv_packed, key_mask, causal):
+        if kv_packed or key_mask is not None or causal or B % G:
+            raise ValueError(f"attention with shared keys / values (kv_group={G}): cross-attention only (no key mask, not causal, keys not the "
+                             f"packed rows) on a whole number of images (B={B})")
+        return B // G, G
+
     def attn_backward(self, q, k, v, out, dout, lse, B, H, Tq, Tk, *, ldq, ldk, ldv, ldo, lddo, grads=None, ldg=None, grads8=None, pack=None,
-                      kv_packed=False, key_mask=None, causal=False):
-        """the backward of `attn_forward` (same pack / kv_packed / key_mask / causal).  Either grads = (dq, dk, dv) with their row strides
-        ldg, or grads8 = (dQ's `fp8_out`, dK's `fp8_out`, dV's fp8 view): the gradients leave as fp8 bytes, one 64x64 tile only."""
+                      kv_packed=False, key_mask=None, causal=False, kv_group=1):
+        """the backward of `attn_forward` (same pack / kv_packed / key_mask / causal / kv_group).  Either grads = (dq, dk, dv) with their
+        row strides ldg, or grads8 = (dQ's `fp8_out`, dK's `fp8_out`, dV's fp8 view): the gradients leave as fp8 bytes, one 64x64 tile
+        only.  kv_group = G > 1: dk / dv [n_img * Tk rows] are the sums over an image's G captions (no fp8 emission)."""
         q_off, q_len = (None, None) if pack is None else pack[:2]
+        if kv_group > 1:
+            n_img, G = self._kv_group_call(B, kv_group, kv_packed, key_mask, causal)
+            if grads8 is not None:
+                raise ValueError("attention backward with shared keys / values: no fp8 emission of dK / dV")
+            ld = dict(ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, lddo=lddo, lddq=ldg[0], lddk=ldg[1], lddv=ldg[2])
+            if not (packed_attn_tiled(Tq, Tk) or self.attn_shared_tiled):
+                ops.attn_bwd_shared(q, k, v, out, dout, lse, *grads, n_img, G, H, Tq, Tk, q_off=q_off, q_len=q_len, **ld)
+            elif pack is None:
+                ops.attn_bwd(q, k, v, out, dout, lse, *grads, n_img, H, G * Tq, Tk, **ld)
+            else:
+                ops.attn_bwd_packed_tiled(q, k, v, out, dout, lse, *grads, n_img, H, G * Tq, Tk, pack[3], pack[4], kv_packed=False, **ld)
+            return
         if grads8 is not None:
             if packed_attn_tiled(Tq, Tk):
                 raise ValueError(f"attention backward: fp8 emission needs one 64x64 tile per sequence (Tq={Tq} Tk={Tk})")
@@ -618,8 +655,24 @@ class Engine(Fp8Views):
         self._done("patch.w")
 
     # ------------------------------------------------------------------ decoder (teacher forced)
-    def decoder_forward(self, ids, pos_ids, key_mask, ehs, B: int, T: int, save: bool, seed: Optional[int], pack=None):
-        """ids/pos_ids/key_mask int32 [B*T]/[B*T]/[B,T]; ehs [B*S,d].  Returns final-layer-normed hidden [B*T,d].
+    def _kv_group(self, B: int, images, pack=None) -> int:
+        """captions per image of a pass over B caption rows and `images` distinct images (None: B)"""
+        if images is None or images == B:
+            return 1
+        if images < 1 or B % images:
+            raise ValueError(f"{B} caption rows do not divide over {images} images")
+        if self.fp8:
+            raise ValueError("several captions per image are not supported together with fp8 GEMMs (the fused e5m2 emission of the "
+                             "cross-attention's dK / dV has no shared form)")
+        if pack is not None and len(pack) < 5:
+            raise ValueError("packed rows with several captions per image: pack = (q_off, q_len, rows, q_off_img, q_len_img) — the last "
+                             "two from train.group_packed_rows")
+        return B // images
+
+    def decoder_forward(self, ids, pos_ids, key_mask, ehs, B: int, T: int, save: bool, seed: Optional[int], pack=None, images=None):
+        """ids/pos_ids/key_mask int32 [B*T]/[B*T]/[B,T]; ehs [images*S,d].  Returns final-layer-normed hidden [B*T,d].
+        images (None = B): the number of distinct images — caption row r attends image r // (B // images); the cross k/v projections
+        run at images*S rows and the cross-attention shares them (`attn_forward(kv_group=...)`).
 
         pack = (q_off int32 [B], q_len int32 [B], rows): PACKED rows — the decoder runs on the `rows` = sum(q_len) valid positions
         only (sequence b = rows [q_off[b], q_off[b] + q_len[b]); ids / pos_ids are then the packed arrays, key_mask is unused:
@@ -628,7 +681,8 @@ class Engine(Fp8Views):
         gradient is exactly zero: leaving them out changes no result.  Buffers keep their [B*T] capacity."""
         P = self.P
         d, f, H, S = P.d, P.ffn, P.H, P.S
-        Mcap, Mv = B * T, B * S
+        G = self._kv_group(B, images, pack)
+        Mcap, Mv = B * T, (B // G) * S
         M = pack[2] if pack is not None else Mcap  # rows the kernels process
         drop = seed is not None and self.p_drop > 0
 
@@ -665,7 +719,7 @@ class Engine(Fp8Views):
                 self.linear(ehs, p + "ckv", kv, Mv, save_tag="d.ehs." if save else None, stable_input=True)
             cctx = self.buf(tag + "cctx", Mcap, d)
             clse = self.vec(tag + "clse", B * H * T)
-            self.attn_forward(q, kv, kv[:, d:], cctx, clse, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, pack=pack)
+            self.attn_forward(q, kv, kv[:, d:], cctx, clse, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, pack=pack, kv_group=G)
             x2 = self.buf(tag + "x2", Mcap, d)
             self.linear(cctx, p + "co", x2, M, residual=x1, drop_seed=sd(11 + 3 * l))
             a, a8 = self.ln_q8(x2, p + "ln_ff", self.dec_eps, tag + "a_ff", Mcap, stats[4], stats[5], M, p + "fc1", tag)
@@ -750,13 +804,15 @@ class Engine(Fp8Views):
             return None  # the fp32 (parity) GEMM kernel has no by-products: its consumers stream the logits
         return self.buf(name + ".stat", M, 2 * (self.P.Vpad // 64), torch.float32)  # (max, sum exp) per 64-column granule
 
-    def decoder_backward(self, B: int, T: int, ids, pos_ids, key_mask, ehs, dlogits, seed: Optional[int], rows=None, pack=None):
+    def decoder_backward(self, B: int, T: int, ids, pos_ids, key_mask, ehs, dlogits, seed: Optional[int], rows=None, pack=None, images=None):
         """Consumes dlogits [M,Vpad] (or [Mc,Vpad] for the compacted head: rows = (idx int32 [Mc], Mc)); writes all
-        decoder/embedding/head grads; returns dehs [B*S,d].  pack: see decoder_forward (the compacted head's rows ARE the packed
-        rows then: no gather / scatter between the head and the decoder)."""
+        decoder/embedding/head grads; returns dehs [images*S,d].  pack: see decoder_forward (the compacted head's rows ARE the packed
+        rows then: no gather / scatter between the head and the decoder).  images: see decoder_forward — dK / dV of the cross-attention
+        arrive summed over an image's captions, so the ckv dX / dW GEMMs and dehs have images*S rows."""
         P = self.P
         d, f, H, S = P.d, P.ffn, P.H, P.S
-        Mcap, Mv = B * T, B * S
+        G = self._kv_group(B, images, pack)
+        Mcap, Mv = B * T, (B // G) * S
         M = pack[2] if pack is not None else Mcap
         drop = seed is not None and self.p_drop > 0
         pd = self.p_drop if drop else 0.0
@@ -913,7 +969,8 @@ class Engine(Fp8Views):
                 dq, dq8, dkv8 = self.dyb("db.dq", l, Mcap, d), None, None
                 dkv = dkvcat[:, l * 2 * d:] if hoist else self.dyb("db.dkv", l, Mv, 2 * d)
                 grads = dict(grads=(dq, dkv, dkv[:, d:]), ldg=(d, ldkv, ldkv))
-            self.attn_backward(cq, ckv, ckv[:, d:], cctx, dctx, clse, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lddo=d, pack=pack, **grads)
+            self.attn_backward(cq, ckv, ckv[:, d:], cctx, dctx, clse, B, H, T, S, ldq=d, ldk=ldkv, ldv=ldkv, ldo=d, lddo=d, pack=pack, kv_group=G,
+                               **grads)
             self.linear_bwd(p + "cq", a_ca, dq, M, dx=da, defer=True, dy8=dq8, par=self._par(l))
             if not hoist:
                 self.linear_bwd(p + "ckv", ehs, dkv, Mv, dx=dehs, dx_accumulate=(l != P.L - 1), defer=True, dy8=dkv8, par=self._par(l))
@@ -1109,10 +1166,10 @@ class Engine(Fp8Views):
         self._ET_version, self._ET_event = version, done
 
     # ------------------------------------------------------------------ full passes
-    def forward_logits(self, pixels, ids, pos_ids, key_mask, B, T, *, save=False, seed=None, trunc_int32=False, stats=False):
+    def forward_logits(self, pixels, ids, pos_ids, key_mask, B, T, *, save=False, seed=None, trunc_int32=False, stats=False, images=None):
         self._fp8_begin_pass()
         _, ehs = self.vit_forward(pixels, save, trunc_int32)
-        hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, save, seed)
+        hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, save, seed, images=images)
         if stats:
             logits, stat = self.head_logits(hf, B * T, stats=True, fp8=True)
             return logits, ehs, stat
@@ -1139,18 +1196,27 @@ class Engine(Fp8Views):
             ops.zero(logits[Mc:Mcp])  # reduction padding of the dE GEMM (rows of an earlier, longer batch may linger here)
         return logits, stat
 
-    def loss_only(self, pixels, ids, pos_ids, key_mask, labels, B, T, *, label_smoothing=0.0, rows=None, row_labels=None, pack=None):
-        """eval_step's forward + loss (main.py:710-716)."""
+    def loss_only(self, pixels, ids, pos_ids, key_mask, labels, B, T, *, label_smoothing=0.0, rows=None, row_labels=None, pack=None,
+                  images=None):
+        """eval_step's forward + loss (main.py:710-716).  images: see loss_and_grads."""
         M = B * T
         pack = self._check_pack(pack, rows, T)
+        self._check_images(pixels, B, images, pack)
         if rows is None:
-            logits, _, stat = self.forward_logits(pixels, ids, pos_ids, key_mask, B, T, save=False, seed=None, stats=True)
+            logits, _, stat = self.forward_logits(pixels, ids, pos_ids, key_mask, B, T, save=False, seed=None, stats=True, images=images)
             return self.loss_and_dlogits(logits, labels, key_mask.reshape(-1), M, label_smoothing, backward=False, stat=stat)
         self._fp8_begin_pass()
         _, ehs = self.vit_forward(pixels, False)
-        hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, False, None, pack=pack)
+        hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, False, None, pack=pack, images=images)
         logits, stat = self.compact_head(hf, M, rows, packed=pack is not None)
         return self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=False, stat=stat)
+
+    def _check_images(self, pixels, B: int, images, pack):
+        """the pass over B caption rows takes `images` distinct images (None: B): checked before anything is launched"""
+        n = B if images is None else images
+        if pixels.shape[0] != n:
+            raise ValueError(f"pixels hold {pixels.shape[0]} images, the pass expects {n} (B={B}, images={images})")
+        self._kv_group(B, images, pack)
 
     def _check_pack(self, pack, rows, T: int):
         """packed rows need the bf16-storage kernels (bf16 or fp8 GEMMs) and the compacted head on the same rows; any seq_len and any
@@ -1173,28 +1239,33 @@ class Engine(Fp8Views):
         return t[:n]
 
     def loss_and_grads(self, pixels, ids, pos_ids, key_mask, labels, B, T, *, label_smoothing=0.0, seed=None, rows=None,
-                       row_labels=None, pack=None):
+                       row_labels=None, pack=None, images=None):
         """value_and_grad(compute_loss) of train_step (main.py:688-697): grads land in ParamStore.grad.
         rows = (idx int32 [Mc] of the positions with loss mask 1, Mc) and row_labels = labels[idx] switch the LM head,
-        the cross-entropy and their backward to those rows only (identical loss and gradients, ~(1 - Mc/M) less head work)."""
+        the cross-entropy and their backward to those rows only (identical loss and gradients, ~(1 - Mc/M) less head work).
+        images (None = B): the number of distinct images in `pixels` — G = B // images captions per image, caption row r belongs to
+        image r // G.  The step is the one on pixels.repeat_interleave(G, 0): the image tower, the cross k/v projections and their
+        backward run at images*S rows, an image's encoder states receive the sum of its captions' gradients."""
         P = self.P
+        self._check_images(pixels, B, images, None if pack is None else self._check_pack(pack, rows, T))
         P.ensure_grads()
         ops.zero(P.grad[P.atomic_begin:])
         M = B * T
         pack = self._check_pack(pack, rows, T)
         if rows is None:
-            logits, ehs, stat = self.forward_logits(pixels, ids, pos_ids, key_mask, B, T, save=True, seed=seed, stats=True)
+            logits, ehs, stat = self.forward_logits(pixels, ids, pos_ids, key_mask, B, T, save=True, seed=seed, stats=True, images=images)
             loss = self.loss_and_dlogits(logits, labels, key_mask.reshape(-1), M, label_smoothing, backward=True, stat=stat)
         else:
             self._fp8_begin_pass()
             _, ehs = self.vit_forward(pixels, True)
-            hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, True, seed, pack=pack)
+            hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, True, seed, pack=pack, images=images)
             logits, stat = self.compact_head(hf, M, rows, packed=pack is not None)
             loss = self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=True, stat=stat)
-        dehs = self.decoder_backward(B, T, ids, pos_ids, key_mask, ehs, logits, seed, rows=rows, pack=pack)
+        dehs = self.decoder_backward(B, T, ids, pos_ids, key_mask, ehs, logits, seed, rows=rows, pack=pack, images=images)
+        n_img = B if images is None else images
         if self.skip_vit_backward:
-            self.vit_backward_bridge(B, dehs)
+            self.vit_backward_bridge(n_img, dehs)
         else:
-            self.vit_backward(B, dehs)
+            self.vit_backward(n_img, dehs)
         self.dw_join()
         return loss

@@ -282,6 +282,21 @@ def attn_bwd_packed_tiled(q, k, v, out, dout, lse, dq, dk, dv, B, H, Tq_max, Tk,
                                               _stream()), "mic_attn_bwd_packed_tiled")
 
 
+def attn_fwd_shared(q, k, v, out, n_img, G, H, Tq_max, Tk, *, ldq, ldk, ldv, ldo, q_off=None, q_len=None, lse=None):
+    """one-tile cross-attention of n_img * G query sequences (image-major; dense rows, or packed rows with q_off / q_len) over the Tk
+    dense key / value rows of their image"""
+    L.check(L.lib().mic_attn_fwd_shared(_dt(q), n_img, G, H, Tq_max, Tk, _p(q_off), _p(q_len), _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo,
+                                        _p(lse), _stream()), "mic_attn_fwd_shared")
+    return out
+
+
+def attn_bwd_shared(q, k, v, out, dout, lse, dq, dk, dv, n_img, G, H, Tq_max, Tk, *, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, q_off=None,
+                    q_len=None):
+    """the backward of attn_fwd_shared: dq per caption, dk / dv [n_img * Tk rows] summed over an image's G captions inside the kernel"""
+    L.check(L.lib().mic_attn_bwd_shared(_dt(q), n_img, G, H, Tq_max, Tk, _p(q_off), _p(q_len), _p(q), ldq, _p(k), ldk, _p(v), ldv, _p(out), ldo,
+                                        _p(dout), lddo, _p(lse), _p(dq), lddq, _p(dk), lddk, _p(dv), lddv, _stream()), "mic_attn_bwd_shared")
+
+
 def attn_bwd_q8(q, k, v, out, dout, lse, dq8, dk8, dv8, B, H, Tq, Tk, *, ldq, ldk, ldv, ldo, lddo, q_off=None, q_len=None, kv_packed=False,
                 key_mask=None, causal=False):
     """attention backward (bf16, one 64x64 tile per sequence; dense rows, or packed rows with q_off / q_len) whose dQ / dK / dV leave

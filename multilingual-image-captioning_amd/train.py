@@ -77,6 +77,37 @@ def packed_rows(attention_mask, decoder_input_ids):
     return off, ln, ids, pos
 
 
+def group_packed_rows(q_off, q_len, captions_per_image: int):
+    """Packed rows of G = captions_per_image captions per image, image-major (caption b belongs to image b // G): an image's G
+    captions are consecutive packed rows, so for the cross-attention — which couples no two queries — image i is ONE sequence of
+    q_len'[i] = sum_g q_len[i*G + g] rows starting at q_off'[i] = q_off[i*G].  Returns (q_off', q_len') int32 [B // G]; G = 1 is the
+    identity.  Pure host function (numpy)."""
+    off, ln = np.asarray(q_off, dtype=np.int32), np.asarray(q_len, dtype=np.int32)
+    G = int(captions_per_image)
+    if G < 1 or off.shape != ln.shape or off.ndim != 1 or off.size % G:
+        raise ValueError(f"group_packed_rows: {off.size} sequences do not divide into groups of {captions_per_image}")
+    if off.size and not np.array_equal(off[1:], (off + ln)[:-1]):
+        raise ValueError("group_packed_rows: the packed sequences must follow one another without gaps (packed_rows' layout)")
+    return off[::G].copy(), ln.reshape(-1, G).sum(1).astype(np.int32)
+
+
+def check_captions_per_image(batch, fp8: bool = False) -> int:
+    """batch["captions_per_image"] = G (absent: 1), checked on the host before anything touches a device: an int >= 1, caption
+    rows == images * G, and no fp8 GEMMs with G > 1.  Returns G."""
+    G = batch.get("captions_per_image", 1)
+    if isinstance(G, (bool, np.bool_)) or not isinstance(G, (int, np.integer)) or G < 1:
+        raise ValueError(f"batch['captions_per_image'] must be an integer >= 1, got {G!r}")
+    G = int(G)
+    n_img, n_cap = int(batch["pixel_values"].shape[0]), int(batch["input_ids"].shape[0])
+    if n_cap != n_img * G:
+        raise ValueError(f"batch['captions_per_image'] = {G}: {n_img} images need {n_img * G} caption rows (image-major: row r belongs to "
+                         f"image r // {G}), got {n_cap}")
+    if G > 1 and fp8:
+        raise ValueError("captions_per_image > 1 is not supported together with gemm_dtype='fp8' (out of scope: the fused e5m2 emission "
+                         "of the cross-attention's dK / dV has no shared form)")
+    return G
+
+
 def plan_buckets(numel: int, bucket_elems: int, boundaries: List[int], max_elems: int = 0,
                  splittable: Tuple[Tuple[int, int, int], ...] = ()) -> List[Tuple[int, int]]:
     """Contiguous [begin, end) slices of the flat gradient buffer, cut at segment boundaries, each >= bucket_elems
@@ -943,6 +974,9 @@ class Trainer:
 
     def _prep(self, batch):
         m = self.model
+        # several captions per image: G caption rows per image, image-major (refusals come before any device work)
+        G = check_captions_per_image(batch, bool(getattr(m.engine, "fp8", False)))
+        self._images = int(batch["pixel_values"].shape[0]) if G > 1 else None
         px = m._dev(batch["pixel_values"], torch.float32)
         labels = m._dev(batch["input_ids"], torch.int32)
         mask = m._dev(batch["attention_mask"], torch.int32)
@@ -981,8 +1015,13 @@ class Trainer:
                 n_pk = int(np.asarray(ql).sum()) if not isinstance(ql, torch.Tensor) else int(ql.sum())
                 if n_pk != rows[1]:
                     raise ValueError(f"batch['packed_rows'] describes {n_pk} decoder rows but batch['loss_rows'] has {rows[1]}: both must come from the same attention_mask")
+            grouped = ()
+            if G > 1:
+                # the cross-attention beyond one tile takes an image's captions as one sequence: its description, from the host copies
+                host = [t.cpu().numpy() if isinstance(t, torch.Tensor) else t for t in pk[:2]]
+                grouped = tuple(m._dev(t, torch.int32) for t in group_packed_rows(host[0], host[1], G))
             q_off, q_len, ids_p, pos_p = (m._dev(t, torch.int32) for t in pk)
-            self._pack = ((q_off, q_len, rows[1]), ids_p, pos_p)
+            self._pack = ((q_off, q_len, rows[1]) + grouped, ids_p, pos_p)
         self._rows, self._row_labels = rows, row_labels
         return px, labels, mask, dec_in, pos, B, T
 
@@ -1007,7 +1046,10 @@ class Trainer:
         self._hyper_ev[slot] = ev
 
     def train_step(self, batch: Dict) -> Dict[str, float]:
-        """main.py:684-707."""
+        """main.py:684-707.  batch["captions_per_image"] = G (optional, an int >= 1): `pixel_values` holds n_img images, the caption
+        tensors (and "loss_rows" / "packed_rows") n_img * G rows, image-major — caption row r belongs to image r // G.  The step is the
+        one on pixel_values.repeat_interleave(G, 0) with the image tower and the cross k/v projections run once per image; refused
+        (ValueError, before any device work): a G that is no int >= 1, caption rows != n_img * G, G > 1 with fp8 GEMMs."""
         # (a micro-step that only accumulates issues no collective: the planner keeps all CUs there)
         budget = self._cu_budget if not (self.accumulate_steps > 1 and self._micro < self.accumulate_steps - 1) else 0
         if budget:
@@ -1067,10 +1109,11 @@ class Trainer:
                 if self._pack is not None:  # the decoder sees the valid positions only
                     pack, ids_p, pos_p = self._pack
                     loss = eng.loss_and_grads(px, ids_p, pos_p, None, labels.reshape(-1), B, T, label_smoothing=self.ls, seed=seed,
-                                              rows=self._rows, row_labels=self._row_labels, pack=pack)
+                                              rows=self._rows, row_labels=self._row_labels, pack=pack, images=self._images)
                 else:
                     loss = eng.loss_and_grads(px, dec_in.reshape(-1), pos.reshape(-1), mask, labels.reshape(-1), B, T,
-                                              label_smoothing=self.ls, seed=seed, rows=self._rows, row_labels=self._row_labels)
+                                              label_smoothing=self.ls, seed=seed, rows=self._rows, row_labels=self._row_labels,
+                                              images=self._images)
             eng.on_embed_rows = None
             if not final:
                 r.finish()
@@ -1136,10 +1179,10 @@ class Trainer:
         if self._pack is not None:
             pack, ids_p, pos_p = self._pack
             loss = eng.loss_only(px, ids_p, pos_p, None, labels.reshape(-1), B, T, label_smoothing=self.ls, rows=self._rows,
-                                 row_labels=self._row_labels, pack=pack)
+                                 row_labels=self._row_labels, pack=pack, images=self._images)
         else:
             loss = eng.loss_only(px, dec_in.reshape(-1), pos.reshape(-1), mask, labels.reshape(-1), B, T, label_smoothing=self.ls,
-                                 rows=self._rows, row_labels=self._row_labels)
+                                 rows=self._rows, row_labels=self._row_labels, images=self._images)
         self.metrics_buf[0:1].copy_(loss)
         self.metrics_buf[1:2].zero_()
         out = self._pmean_metrics()
