@@ -137,6 +137,13 @@ typedef struct {
    * c_q8_amax this pass's partial maxima (or NULL), c_q8_fmt MIC_E4M3 / MIC_E5M2.  Activation / dact epilogues of NT launches
    * (GELU(FFN-in) -> the e4m3 operand of FFN-out; dGELU-scaled dX of FFN-out -> the e5m2 dy of FFN-in's backward). */
   float* c_q8_state; float* c_q8_amax; int c_q8_fmt;
+  /* optional, with rowstat only (bf16 operands, the LM head of a scorer): pick_out[m] = the value of (m, pick_col[m]) AS IT WOULD BE
+   * STORED in C (bf16-rounded), as fp32 — one plain store per row m < M, 0 <= pick_col[m] < rowstat_nvalid (the caller's promise: a
+   * column outside leaves pick_out[m] unwritten).  Both set or neither.  With them C may be NULL: NO C is stored (ldc is ignored), the
+   * launch leaves the softmax partials and the picked values — all mic_ce_rows_picked needs — and 2 N bytes per row stay unwritten.
+   * The launch must be one the planner gives to family 6 (mic_gemm_plan reports epi = 2; K >= 256, K % 128 == 0, MIC_GEMM_D2 != 0):
+   * refused with MIC_EINVAL otherwise, the other kernel families have no such epilogue. */
+  const int32_t* pick_col; float* pick_out;
 } mic_gemm_args;
 int mic_gemm(const mic_gemm_args* a, void* stream);
 /* dst[r][c] (dst_dtype) = sum over s < n_slabs of src[s * slab_stride + r * ld_src + c] (fp32): the second half of a
@@ -163,7 +170,8 @@ int mic_get_cu_budget(void);
  *           switches it off), 6 = the two-blocks-per-CU 256x128 kernel (gemm_d2.hip: by default those of the four-wave kernel's
  *           launches that carry softmax partials; MIC_GEMM_D2);
  *   plain:  1 = every problem on the bare / residual epilogue (the PLAIN instantiation of families 0-4);
- *   epi:    the epilogue instantiation of family 5 (gemm_w4_kernel<2|3|6|7|8>) and 6 (gemm_d2_kernel<0|1>), 0 otherwise;
+ *   epi:    the epilogue instantiation of family 5 (gemm_w4_kernel<2|3|6|7|8>) and 6 (gemm_d2_kernel<0|1|2>; 2 = softmax partials and
+ *           picked values, pick_col / pick_out), 0 otherwise;
  *   tile_m x tile: tile rows x columns (64 / 128 / 256 square, 192 x 128, 256 x 128 for family 6); K-groups per block; logical
  *   blocks; launched grid (persistent launches — PLAIN family 3 with more tiles than CUs —: the budget); blocks of this
  *   configuration that fit one CU;
@@ -410,6 +418,14 @@ int mic_ce_rows(int dtype, int rows, int V, const void* logits, int ld, const in
  * [rows][stat_ld] float2, 64 columns each), row_loss = lse - logits[label] (label_smoothing 0: plain NLL, main.py:674 with a one-hot target) */
 int mic_ce_rows_tiles(int dtype, int rows, int V, const void* logits, int ld, const float* rowstat, int stat_ld,
                       const int32_t* labels, float* row_lse, float* row_loss, void* stream);
+/* mic_ce_rows_tiles with the label's logit read from label_logit[row] (fp32: mic_gemm_args.pick_out of a head launch that stored no
+ * logits) instead of the logits matrix: the same merge of the partials, so row_lse and row_loss have the same bits. */
+int mic_ce_rows_picked(int rows, int V, const float* rowstat, int stat_ld, const float* label_logit, float* row_lse, float* row_loss,
+                       void* stream);
+/* out[s] = scale * sum over i < seg_len[s] of x[seg_off[s] + i] (fp32) for s < n_seg: one wave per segment, lane l adds elements
+ * l, l + 64, ... in order, then a fixed tree over the lanes — the order depends on seg_len[s] alone (same bits whatever the grid), no
+ * atomics; seg_len[s] == 0 gives +0; nothing outside the segments is read.  (Per-caption sums of token log-probabilities.) */
+int mic_segment_sums(int n_seg, const int32_t* seg_off, const int32_t* seg_len, const float* x, float scale, float* out, void* stream);
 int mic_ce_reduce(int rows, const float* row_loss, const int32_t* mask, float* loss_out, float* denom_out,
                   void* stream);
 int mic_ce_bwd(int dtype, int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels,

@@ -34,6 +34,7 @@ class GemmArgs(C.Structure):
         ("a_ln_stats", C.c_void_p), ("a_ln_colsum", C.c_void_p), ("a_ln_width", C.c_int), ("a_ln_eps", C.c_float),
         ("rowsum2", C.c_void_p), ("k_valid", C.c_int),
         ("c_q8_state", C.c_void_p), ("c_q8_amax", C.c_void_p), ("c_q8_fmt", C.c_int),
+        ("pick_col", C.c_void_p), ("pick_out", C.c_void_p),
     ]
 
 
@@ -130,6 +131,8 @@ _SIGS = {
     "mic_embed_rows_add_det_ws": ([_i], C.c_int64),
     "mic_ce_rows": ([_i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _p], C.c_int),
     "mic_ce_rows_tiles": ([_i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p], C.c_int),
+    "mic_ce_rows_picked": ([_i, _i, _p, _i, _p, _p, _p, _p], C.c_int),
+    "mic_segment_sums": ([_i, _p, _p, _p, _f, _p, _p], C.c_int),
     "mic_row_topk_tiles": ([_i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p], C.c_int),
     "mic_row_topk_tiles_mapped": ([_i, _i, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p], C.c_int),
     "mic_ce_reduce": ([_i, _p, _p, _p, _p, _p], C.c_int),

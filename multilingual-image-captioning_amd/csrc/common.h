@@ -313,6 +313,9 @@ struct EpiArgs {
   // see Q8Out above — the GELU output of the FFN-in projection (next: the fp8 FFN-out projection) and the dGELU-scaled dX of
   // FFN-out (next: FFN-in's backward GEMMs)
   int c_q8; float* q8_state; float* q8_amax;
+  // gemm_d2_kernel<2> only (mic_gemm_args.pick_col / pick_out): pick_out[m] = the value of (m, pick_col[m]) as stored; C may be null
+  // there (no C is stored).  LAST in the struct, which is last in Problem: no other field's kernel-argument offset moves.
+  const int32_t* pick_col; float* pick_out;
 };
 template <typename T>
 __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int m, int n, float v) {

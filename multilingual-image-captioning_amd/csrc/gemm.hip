@@ -88,7 +88,14 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 
 // the host checks of one problem (every dtype): what include/mic_hip.h promises to refuse
 static int check_epi(const mic_gemm_args* a) {
-  MIC_CHECK(a && a->A && a->B && a->C, "mic_gemm: null pointer");
+  MIC_CHECK(a && a->A && a->B, "mic_gemm: null pointer");
+  MIC_CHECK((a->pick_col != nullptr) == (a->pick_out != nullptr), "mic_gemm: pick_col and pick_out go together (both set, or neither)");
+  MIC_CHECK(a->C || a->pick_col, "mic_gemm: null pointer (C may be NULL only with pick_col / pick_out: the head launch that stores no logits)");
+  if (a->pick_col) {
+    MIC_CHECK(a->dtype == MIC_BF16, "mic_gemm: pick_col / pick_out need bf16 operands (no fp8 / fp32 form)");
+    MIC_CHECK(a->rowstat, "mic_gemm: pick_col / pick_out go with rowstat (the bare bias epilogue of the bf16 LM head)");
+    MIC_CHECK((((uintptr_t)a->pick_col | (uintptr_t)a->pick_out) & 3) == 0, "mic_gemm: pick_col / pick_out must be 4-B aligned");
+  }
   MIC_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "mic_gemm: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
   MIC_CHECK(a->dtype == MIC_BF16 || a->dtype == MIC_F32 || a->dtype == MIC_FP8, "mic_gemm: bad dtype %d", a->dtype);
   if (a->dtype == MIC_FP8) {
@@ -120,7 +127,7 @@ static int check_epi(const mic_gemm_args* a) {
     MIC_CHECK((a->dtype == MIC_BF16 || (a->dtype == MIC_FP8 && !a->a_kmajor)) && a->c_dtype == MIC_BF16 && a->split_k <= 1 && !a->act && !a->dact && !a->R &&
                   !a->accumulate && a->dropout_p == 0.f && !a->Zout,
               "mic_gemm: rowstat goes with the bare bias epilogue of a bf16 / fp8 NT GEMM with a bf16 C (the LM head)");
-    MIC_CHECK(a->N % 64 == 0 && a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0, "mic_gemm: rowstat needs N %% 64 == 0 and a 16-B aligned C");
+    MIC_CHECK(a->N % 64 == 0 && (!a->C || (a->ldc % 8 == 0 && ((uintptr_t)a->C & 15) == 0)), "mic_gemm: rowstat needs N %% 64 == 0 and a 16-B aligned C");
     MIC_CHECK(a->rowstat_ld >= a->N / 64 && ((uintptr_t)a->rowstat & 7) == 0, "mic_gemm: rowstat needs ld >= N / 64 float2 entries per row");
   }
   if (a->a_ln_stats) {
@@ -152,12 +159,13 @@ static int check_epi(const mic_gemm_args* a) {
 // the epilogue of one problem as the kernels read it: no checks, no pointer is dereferenced (mic_gemm_plan fills it from argument
 // sets that check_epi would refuse)
 static void fill_epi(const mic_gemm_args* a, EpiArgs& e) {
-  e.C = a->C; e.ldc = a->ldc; e.c_f32 = (a->c_dtype == MIC_F32);
+  const int ldc = a->C ? a->ldc : 0;  // (no C: a pick launch that stores none — ldc is ignored)
+  e.C = a->C; e.ldc = ldc; e.c_f32 = (a->c_dtype == MIC_F32);
   e.c_q8 = a->c_dtype == MIC_FP8 ? 1 + a->c_q8_fmt : 0; e.q8_state = a->c_q8_state; e.q8_amax = a->c_q8_amax;
   e.bias = a->bias; e.act = a->act; e.Zout = a->Zout; e.ldz = a->ldz; e.Zin = a->Zin; e.dact = a->dact;
   // 16-B vector epilogue: leading dimensions multiples of 8 and every touched base address aligned (an fp8 C is written 8 bytes at
   // a time); anything else takes the elementwise path
-  e.vec = a->ldc % 8 == 0 && (!(a->Zout || a->Zin) || a->ldz % 8 == 0) && (!a->R || a->ldr % 8 == 0) &&
+  e.vec = ldc % 8 == 0 && (!(a->Zout || a->Zin) || a->ldz % 8 == 0) && (!a->R || a->ldr % 8 == 0) &&
           (((uintptr_t)a->Zout | (uintptr_t)a->Zin | (uintptr_t)a->R) & 15) == 0 && ((uintptr_t)a->C & (a->c_dtype == MIC_FP8 ? 7 : 15)) == 0;
   e.R = a->R; e.ldr = a->ldr; e.accumulate = a->accumulate;
   e.drop_thr = a->dropout_p > 0.f ? (uint32_t)fminf(a->dropout_p * 4294967296.0f, 4294967295.0f) : 0u;
@@ -166,6 +174,7 @@ static void fill_epi(const mic_gemm_args* a, EpiArgs& e) {
   e.rowstat = a->rowstat; e.stat_ld = a->rowstat_ld; e.stat_nvalid = a->rowstat_nvalid > 0 ? a->rowstat_nvalid : a->N;
   e.ln_stats = a->a_ln_stats; e.ln_g = a->a_ln_colsum; e.ln_bias = nullptr; e.ln_inv_d = 0.f; e.ln_eps = a->a_ln_eps;
   e.rowsum2 = a->rowsum2;
+  e.pick_col = a->pick_col; e.pick_out = a->pick_out;
   if (a->a_ln_stats) { e.ln_bias = a->bias; e.bias = nullptr; e.ln_inv_d = 1.0f / (float)a->a_ln_width; }
 }
 
@@ -400,6 +409,11 @@ static int launch_bf16(const mic_gemm_args* args, int count, hipStream_t s) {
   fill_table(args, count, tab);
   const GemmDecision d = decide(args, count, tab);
   if (int rc = check_table(args, count, tab, d.plain)) return rc;
+  // picked values (and a launch without C) exist in ONE epilogue, gemm_d2_kernel<2>: every other decision is refused, nothing is launched
+  for (int i = 0; i < count; ++i)
+    MIC_CHECK(!args[i].pick_col || (d.family == GEMM_D2 && d.epi == 2),
+              "mic_gemm: pick_col / pick_out need a launch the planner gives to family 6 (one bf16 NT problem, K >= 256, K %% 128 == 0, "
+              "MIC_GEMM_D2 != 0): M=%d N=%d K=%d goes to family %d — ask mic_gemm_plan first", args[i].M, args[i].N, args[i].K, d.family);
   switch (d.family) {
     case GEMM_D2: launch_gemm_d2(tab, d, s); break;          // 256x128, 4 waves, two blocks per CU
     case GEMM_W4: launch_gemm_w4(tab, d, s); break;          // 256x256, 4 waves x 128x128

@@ -42,6 +42,7 @@ void launch_gemm_w4(const LaunchTable& tab, const GemmDecision& d, hipStream_t s
 // gemm_d2.hip: 256x128 tiles on four waves (128x64 wave tiles), two blocks per CU, LDS-DMA ring of 32-k steps; NT, single problem
 int gemm_d2_takes(const LaunchTable& tab);
 void launch_gemm_d2(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
+void launch_gemm_d2_pick(const LaunchTable& tab, hipStream_t s);  // gemm_d2_pick.hip: gemm_d2_kernel<2> (picked values, optional C)
 // one translation unit per tile configuration of the main kernel (gemm_kernel.h): 256x256 / 128x128 (K-groups 1, 2) / 64x64 (1, 2, 4)
 void launch_gemm_t256(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);
 void launch_gemm_t128(const LaunchTable& tab, const GemmDecision& d, hipStream_t s);

@@ -16,7 +16,8 @@
 //     Requests run two steps ahead of their first read; a fragment register is re-read half a step behind its last use (48 VGPRs of
 //     fragments in all).  Past the end of K the requests go through a zero-record resource (dropped, still counted by vmcnt).
 //   * Epilogue per wave, no block barrier: four passes of 32 rows through a private fp32 LDS image, read back as (row, 8 columns)
-//     units.  Bare launches (bf16 C = alpha acc + bias, optional softmax partials) store straight away; everything else — activation,
+//     units.  Bare launches (bf16 C = alpha acc + bias, optional softmax partials; <2>: also each row's picked value, and no C at all
+//     when the caller passes none — the scorer's head, mic_gemm_args.pick_col) store straight away; everything else — activation,
 //     saved pre-activation, dGELU, dropout, residual, fp32 C, accumulate — goes through the shared per-unit helpers with the side
 //     operands of a pass requested before its restage.  With a second block computing on the same CU the epilogue is cover, not
 //     a stall, so it can afford the general form.
@@ -56,8 +57,11 @@ __device__ __forceinline__ uint32_t d2_source(int ld, int x0, int lim, int q, in
 
 // one 32-row pass of the epilogue: the wave's accumulator blocks accp[0..1] (rows mp .. mp+31, columns nw .. nw+63) through the
 // wave's private LDS image Cw
-template <bool STATS>
+// MODE 0: no by-products; 1: softmax partials (E.rowstat); 2: partials and the picked value of every row (E.pick_col -> E.pick_out),
+// bare by construction, C stored only where there is one (gemm_d2_takes)
+template <int MODE>
 __device__ __forceinline__ void d2_epilogue_pass(f32x16 (&accp)[2], const EpiArgs& E, float* Cw, int M, int N, int mp, int nw, int lane, bool bare) {
+  constexpr bool STATS = MODE != 0, PICK = MODE == 2;
   const int urow = lane >> 3, c8 = (lane & 7) * 8;
   const int n = nw + c8;
   const bool nok = n + 8 <= N;  // (the launcher admits N % 8 == 0 only: a unit is inside or outside as a whole)
@@ -69,6 +73,14 @@ __device__ __forceinline__ void d2_epilogue_pass(f32x16 (&accp)[2], const EpiArg
       const int m = mp + it * 8 + urow;
       zq[it] = rq[it] = u32x4{0u, 0u, 0u, 0u};
       if (m < M && nok) epilogue_prefetch8(E, m, n, zq[it], rq[it]);
+    }
+  }
+  int pc[4];  // PICK: the picked column of this lane's four rows, requested before the restage (the 8 lanes of a row read one address)
+  if constexpr (PICK) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int m = mp + it * 8 + urow;
+      pc[it] = m < M ? E.pick_col[m] : -1;
     }
   }
 #pragma unroll
@@ -91,7 +103,15 @@ __device__ __forceinline__ void d2_epilogue_pass(f32x16 (&accp)[2], const EpiArg
       uint4 u;  // the values as stored
       u.x = f2bf_pk(v[0], v[1]); u.y = f2bf_pk(v[2], v[3]);
       u.z = f2bf_pk(v[4], v[5]); u.w = f2bf_pk(v[6], v[7]);
-      if (ok) *reinterpret_cast<uint4*>((uint16_t*)E.C + (size_t)m * E.ldc + n) = u;
+      if (ok && (!PICK || E.C)) *reinterpret_cast<uint4*>((uint16_t*)E.C + (size_t)m * E.ldc + n) = u;
+      if constexpr (PICK) {
+        // the lane whose unit holds the row's picked column writes it: one plain store per row (rows >= M carry pc = -1)
+        const int dcol = pc[it] - n;
+        if (ok && (unsigned)dcol < 8u) {
+          const uint32_t wd = dcol < 2 ? u.x : (dcol < 4 ? u.y : (dcol < 6 ? u.z : u.w));
+          E.pick_out[m] = bf2f((uint16_t)((dcol & 1) ? wd >> 16 : wd & 0xffffu));
+        }
+      }
       if constexpr (STATS) {
         // (max, sum exp(x - max)) of the values AS STORED over this row's 64-column granule = the wave tile's width = 8 consecutive lanes
         const uint32_t w[4] = {u.x, u.y, u.z, u.w};
@@ -103,7 +123,7 @@ __device__ __forceinline__ void d2_epilogue_pass(f32x16 (&accp)[2], const EpiArg
   }
 }
 
-template <bool STATS>
+template <int MODE>
 __device__ __forceinline__ void d2_epilogue(f32x16 (&acc)[4][2], const Problem& P, char* smem, int mw, int nw, int split, int wave, int lane) {
   EpiArgs E = P.epi;
   const int M = P.M, N = P.N;
@@ -125,14 +145,14 @@ __device__ __forceinline__ void d2_epilogue(f32x16 (&acc)[4][2], const Problem& 
     E.bias = nullptr;
   }
   if (E.c_f32) E.C = (float*)E.C + (size_t)split * (size_t)P.split_stride;
-  const bool bare = !E.c_f32 && !E.act && !E.Zout && !E.dact && !E.R && !E.drop_thr && !E.accumulate;
+  const bool bare = MODE == 2 || (!E.c_f32 && !E.act && !E.Zout && !E.dact && !E.R && !E.drop_thr && !E.accumulate);
   float* Cw = reinterpret_cast<float*>(smem) + wave * (32 * D2_EP);
   // one call per 32-row pass with the accumulator rows named by a CONSTANT (a pass loop the compiler does not unroll turns the
   // index into a run-time value and the accumulators into scratch: tests/test_kernel_resources_cpu.py)
-  d2_epilogue_pass<STATS>(acc[0], E, Cw, M, N, mw, nw, lane, bare);
-  d2_epilogue_pass<STATS>(acc[1], E, Cw, M, N, mw + 32, nw, lane, bare);
-  d2_epilogue_pass<STATS>(acc[2], E, Cw, M, N, mw + 64, nw, lane, bare);
-  d2_epilogue_pass<STATS>(acc[3], E, Cw, M, N, mw + 96, nw, lane, bare);
+  d2_epilogue_pass<MODE>(acc[0], E, Cw, M, N, mw, nw, lane, bare);
+  d2_epilogue_pass<MODE>(acc[1], E, Cw, M, N, mw + 32, nw, lane, bare);
+  d2_epilogue_pass<MODE>(acc[2], E, Cw, M, N, mw + 64, nw, lane, bare);
+  d2_epilogue_pass<MODE>(acc[3], E, Cw, M, N, mw + 96, nw, lane, bare);
 }
 
 template <int EPI>
@@ -266,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void gemm_d2_kernel(LaunchTable tab) {
   }
   __syncthreads();
   MIC_TRACE(2);
-  if (live) d2_epilogue<(EPI & 1) != 0>(acc, P, smem, m0 + wr * WM, n0 + wc * WN, split, wave, lane);
+  if (live) d2_epilogue<EPI>(acc, P, smem, m0 + wr * WM, n0 + wc * WN, split, wave, lane);
 #ifdef MIC_TRACE_BLOCKS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the stamp below = this wave's stores acknowledged)
 #endif
@@ -293,9 +313,15 @@ void launch_d2(const LaunchTable& tab, hipStream_t s) {
 
 }  // namespace
 
+// gemm_d2_pick.hip includes this file with MIC_D2_PICK_UNIT defined and instantiates gemm_d2_kernel<2> there (a unit with a resource
+// table of its own); this unit holds <0> and <1> and everything the dispatch decision asks
+#ifdef MIC_D2_PICK_UNIT
+void launch_gemm_d2_pick(const LaunchTable& tab, hipStream_t s) { launch_d2<2>(tab, s); }
+#else
 // the launches this kernel takes: one problem, NT, K >= 128, whole 8-column units with 16-B aligned rows everywhere; no folded
 // LayerNorm / rowsum2 by-products (they stay with the other kernels); split-K as fp32 slabs
-// -> the epilogue instantiation (1 = with softmax partials, 0 = without), or -1: not this kernel's launch
+// -> the epilogue instantiation (2 = softmax partials and picked values, with or without a C; 1 = with softmax partials, 0 = without),
+// or -1: not this kernel's launch
 int gemm_d2_takes(const LaunchTable& tab) {
   if (tab.count != 1) return -1;
   const Problem& p = tab.p[0];
@@ -303,17 +329,19 @@ int gemm_d2_takes(const LaunchTable& tab) {
   const long long lim = 0x7fffffffLL;  // buffer resources with 32-bit lane offsets (gemm_w4.hip)
   if ((long long)p.M * p.lda * 2 >= lim || (long long)p.N * p.ldb * 2 >= lim) return -1;
   if (p.K < 128 || p.K % 64 != 0 || p.N % 8 != 0 || e.rowsum2 || e.ln_stats) return -1;
-  if (((uintptr_t)e.C & 15) != 0 || (e.ldc & 7) != 0) return -1;
+  if (((uintptr_t)e.C & 15) != 0 || (e.ldc & 7) != 0) return -1;  // (no C, a pick launch: null and fill_epi's ldc = 0 pass)
+  if ((e.pick_col != nullptr) != (e.pick_out != nullptr) || (e.pick_col && !e.rowstat)) return -1;  // (a null C without them: check_epi)
   if ((e.Zout || e.Zin) && ((e.ldz & 7) != 0 || ((uintptr_t)(e.Zout ? e.Zout : e.Zin) & 15) != 0)) return -1;
   if (e.R && ((e.ldr & 7) != 0 || ((uintptr_t)e.R & 15) != 0)) return -1;
   if (e.dact && e.accumulate && !e.c_f32) return -1;  // (epilogue_pre_ok)
   if (!e.vec) return -1;  // its side loads are 16-B vectors: every leading dimension and base address aligned (fill_epi)
   if (p.nsplit > 1 && !(e.c_f32 && p.split_stride > 0)) return -1;
   if (e.rowstat && (e.c_f32 || e.act || e.Zout || e.dact || e.R || e.drop_thr || e.accumulate)) return -1;
-  return e.rowstat ? 1 : 0;
+  return e.pick_col ? 2 : (e.rowstat ? 1 : 0);
 }
 void launch_gemm_d2(const LaunchTable& tab, const GemmDecision& d, hipStream_t s) {
-  if (d.epi == 1) launch_d2<1>(tab, s);
+  if (d.epi == 2) launch_gemm_d2_pick(tab, s);  // (gemm_d2_pick.hip)
+  else if (d.epi == 1) launch_d2<1>(tab, s);
   else launch_d2<0>(tab, s);
 }
-
+#endif

@@ -1211,6 +1211,65 @@ class Engine(Fp8Views):
         logits, stat = self.compact_head(hf, M, rows, packed=pack is not None)
         return self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=False, stat=stat)
 
+    # ------------------------------------------------------------------ teacher-forced scores (model.score)
+    SCORE_CHUNK_ROWS = 4096  # materialised scoring head: rows per chunk — its logits never exceed loss_only's buffer for that many rows
+
+    def score_head_free(self, Mc: int) -> bool:
+        """does the scoring head of `Mc` rows run without logits?  bf16 storage with softmax partials, the planner gives the pick launch
+        (ops.gemm pick_col / pick_out, out=None) to gemm_d2_kernel<2>, and MIC_SCORE_HEAD (read here, at call time) does not say
+        `materialised` (A/B runs and tests)."""
+        if self.dt != torch.bfloat16 or not self.use_head_stats or os.environ.get("MIC_SCORE_HEAD", "") == "materialised":
+            return False
+        plan = ops.gemm_plan([(Mc, self.P.Vpad, self.P.d)], kernel=True, pick=True)
+        return plan["family"] == 6 and plan["epi"] == 2
+
+    def score_rows(self, pixels, ids, pos_ids, key_mask, labels, B, T, *, seg, rows=None, row_labels=None, pack=None, images=None):
+        """loss_only's forward (eval mode, no dropout; rows / pack / images as there) with a scorer's tail: returns
+        (token_logprob fp32 [Mc] = -row_loss = log p(label | prefix, image) of the head's rows — the `rows` positions, or all B*T —,
+        sums fp32 [n_seg]).  seg = (seg_off int32 [n_seg], seg_len int32 [n_seg]): sums[s] = the sum of token_logprob over head rows
+        [seg_off[s], seg_off[s] + seg_len[s]) (mic_segment_sums: a caption's valid positions are consecutive head rows).
+        Head: logits-free where `score_head_free` says so — the GEMM leaves softmax partials and each row's label logit, no
+        `d.logits` buffer is touched or allocated (mic_ce_rows_picked) —, else materialised in chunks of SCORE_CHUNK_ROWS rows
+        (mic_ce_rows_tiles / mic_ce_rows with label_smoothing 0).  Both forms give the same bits in bf16 storage."""
+        P = self.P
+        M = B * T
+        pack = self._check_pack(pack, rows, T)
+        self._check_images(pixels, B, images, pack)
+        if self.fp8:
+            raise ValueError("score_rows: scoring with fp8 GEMMs is not supported")
+        _, ehs = self.vit_forward(pixels, False)
+        hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, False, None, pack=pack, images=images)
+        Mc, lab = M, labels
+        if rows is not None:
+            idx, Mc = rows
+            lab = row_labels
+            if pack is None:  # (packed: hf already holds exactly those rows, in that order)
+                hfc = self.buf("d.hfc", M, P.d)
+                ops.copy_rows(hf, hfc, Mc, P.d, src_idx=idx)
+                hf = hfc
+        lse, rl = self.vec("ce.lse", _rup(M, ROWPAD)), self.vec("ce.rowloss", _rup(M, ROWPAD))
+        if self.score_head_free(Mc):
+            stat = self.buf("d.score.stat", M, 2 * (P.Vpad // 64), torch.float32)
+            pick = self.vec("d.score.pick", _rup(M, ROWPAD))
+            ops.gemm(hf, P.w("shared"), None, Mc, P.Vpad, P.d, bias=P.f32("flb"), rowstat=stat, rowstat_nvalid=P.V, pick_col=lab, pick_out=pick)
+            ops.ce_rows_picked(P.V, stat, pick, lse, rl, Mc)
+        else:
+            cap = min(M, self.SCORE_CHUNK_ROWS)
+            logits = self.buf("d.logits", cap, P.Vpad)
+            stat = self.head_stats("d.logits", cap)
+            for r0 in range(0, Mc, cap):
+                n = min(cap, Mc - r0)
+                self._head_project(hf[r0:], logits, n, stat, fp8=False)
+                if stat is not None:
+                    ops.ce_rows_tiles(logits, logits.stride(0), P.V, stat, lab[r0:], lse[r0:], rl[r0:], n)
+                else:
+                    ops.ce_rows(logits, logits.stride(0), P.V, lab[r0:], self.ones_i32(n), 0.0, lse[r0:], rl[r0:], n)
+        seg_off, seg_len = seg
+        n_seg = int(seg_off.numel())
+        sums = self.vec("d.score.sums", n_seg)
+        ops.segment_sums(seg_off, seg_len, rl, sums, n_seg, scale=-1.0)
+        return rl[:Mc].neg(), sums
+
     def _check_images(self, pixels, B: int, images, pack):
         """the pass over B caption rows takes `images` distinct images (None: B): checked before anything is launched"""
         n = B if images is None else images

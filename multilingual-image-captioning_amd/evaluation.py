@@ -131,3 +131,50 @@ def generate_languages(model, pixel_values, lang_ids: Dict[str, int], *, via: st
                          num_return_sequences=num_return_sequences, **{arg: [int(lang_ids[l]) for l in langs]})
     seq = np.asarray(gen.sequences.cpu())
     return {l: seq[g] for g, l in enumerate(langs)}
+
+
+def sequences_to_score_inputs(sequences, eos_token_id: int, pad_token_id: int):
+    """What `model.score` needs to re-score the rows `generate` returned: sequences [R, L] (start token first) ->
+    (decoder_input_ids = seq[:, :-1], labels = seq[:, 1:], attention_mask) as int64 / int64 / int32 numpy arrays [R, L - 1].  The
+    mask covers each row of labels up to and including its first EOS — the positions `generate` summed its `scores` over — or the
+    whole row when it holds none (a caption cut off at max_length).
+    Greedy search and sampling write the EOS they end a row with as PAD (generate's loop: "EOS itself -> PAD"), so a row WITHOUT an
+    EOS that holds a PAD ended at its first PAD: the mask covers the row up to and including that position and the label there is
+    EOS, the token that was drawn.  (A PAD drawn as an ordinary token in the middle of a sampled caption cannot be told from that;
+    with a trained model it has no probability to speak of.)  Behind the mask the labels stay what `generate` left there."""
+    seq = np.asarray(sequences.cpu() if hasattr(sequences, "cpu") else sequences)
+    if seq.ndim != 2 or seq.shape[1] < 2 or not np.issubdtype(seq.dtype, np.integer):
+        raise ValueError(f"sequences_to_score_inputs: integer sequences [rows, length >= 2], got {seq.dtype} {seq.shape}")
+    seq = seq.astype(np.int64)
+    dec_in, labels = seq[:, :-1].copy(), seq[:, 1:].copy()
+    is_eos, is_pad = labels == int(eos_token_id), labels == int(pad_token_id)
+    ended_as_pad = ~is_eos.any(1) & is_pad.any(1)
+    r = np.nonzero(ended_as_pad)[0]
+    labels[r, is_pad[r].argmax(1)] = int(eos_token_id)
+    is_eos = labels == int(eos_token_id)
+    first = np.where(is_eos.any(1), is_eos.argmax(1), labels.shape[1] - 1)
+    mask = (np.arange(labels.shape[1])[None, :] <= first[:, None]).astype(np.int32)
+    return dec_in, labels, mask
+
+
+def rerank_scores(log_likelihood, num_tokens, n_per_image: int, length_penalty: float = 1.0):
+    """The arithmetic of `rerank` on host arrays: scores [images, n] = ll / num_tokens ** length_penalty (a row without tokens
+    scores -inf) and, per image, the index of the best candidate (the first of equals)."""
+    ll = np.asarray(log_likelihood, dtype=np.float64).reshape(-1)
+    nt = np.asarray(num_tokens, dtype=np.float64).reshape(-1)
+    n = int(n_per_image)
+    if n < 1 or ll.shape != nt.shape or ll.size % n:
+        raise ValueError(f"rerank: {ll.size} scored rows do not divide into groups of {n_per_image}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scores = np.where(nt > 0, ll / np.power(np.maximum(nt, 1.0), float(length_penalty)), -np.inf).reshape(-1, n)
+    return scores.argmax(1).astype(np.int64), scores.astype(np.float32)
+
+
+def rerank(model, pixel_values, sequences, n_per_image: int, length_penalty: float = 1.0):
+    """Rerank the n_per_image candidates `generate(num_return_sequences=n)` returned per image (rows image-major: image * n + j) by
+    their teacher-forced log-likelihood, one `model.score` pass in which an image is encoded once for all its candidates.
+    Returns (best int64 [images]: the index j of the best candidate, scores fp32 [images, n] = ll / num_tokens ** length_penalty)."""
+    mc = model.config.mbart_config
+    dec_in, labels, mask = sequences_to_score_inputs(sequences, mc.eos_token_id, mc.pad_token_id)
+    out = model.score(pixel_values, labels, mask, decoder_input_ids=dec_in, candidates_per_image=int(n_per_image))
+    return rerank_scores(out["log_likelihood"].cpu().numpy(), out["num_tokens"].cpu().numpy(), n_per_image, length_penalty)

@@ -235,6 +235,124 @@ class FlaxCLIPVisionMBartForConditionalGeneration(FlaxCLIPVisionMBartPreTrainedM
             res["encoder_attentions"] = att["encoder_attentions"]
         return res if return_dict is not False else res.to_tuple()
 
+    # ------------------------------------------------------------------ score: teacher-forced caption log-likelihoods
+    def score(self, pixel_values, labels, attention_mask=None, *, decoder_input_ids=None, candidates_per_image=1,
+              return_token_logprobs=False, params=None):
+        """How likely is THIS caption for THIS image: log_likelihood[r] = sum over the valid positions t of row r of
+        log p(labels[r, t] | labels[r, <t], image) — one teacher-forced forward in eval mode (no dropout, no label smoothing), the
+        quantity `generate` sums into its `scores` along a decode chain.
+        labels [R, T] with R = images * candidates_per_image, image-major (row r belongs to image r // G: the layout of the
+        Trainer's `captions_per_image` and of `generate(num_return_sequences=N)`); an image is encoded once and its cross-attention
+        k/v projected once for all its candidates.  attention_mask (0/1, default labels != pad_token_id) is the loss mask and the
+        decoder's key mask, as in training; decoder_input_ids default to train.shift_tokens_right(labels, pad).  Prefix masks in
+        bfloat16 storage run on the packed rows; any other mask runs unpacked.
+        Returns ModelOutput(log_likelihood fp32 [R], num_tokens int32 [R][, token_logprobs fp32 [R, T], 0 at masked positions]);
+        a row without a valid token scores 0 with 0 tokens.  ValueError before any device work: R != images * G, G not an
+        int >= 1, label ids outside [0, vocab) on valid positions, T > max_position_embeddings, an engine on fp8 GEMMs."""
+        from .train import group_packed_rows, loss_rows, packed_rows, shift_tokens_right
+
+        def host(x):
+            return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
+
+        mc = self.config.mbart_config
+        G = candidates_per_image
+        if isinstance(G, (bool, np.bool_)) or not isinstance(G, (int, np.integer)) or G < 1:
+            raise ValueError(f"score: candidates_per_image must be an integer >= 1, got {G!r}")
+        G = int(G)
+        if bool(getattr(self.engine, "fp8", False)):
+            raise ValueError("score: not supported with gemm_dtype='fp8' (switch the engine back with set_gemm_dtype)")
+        lab = host(labels)
+        if lab.ndim != 2 or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError(f"score: labels must be integer ids [rows, T], got {lab.dtype} {lab.shape}")
+        R, T = lab.shape
+        n_img = int(pixel_values.shape[0])
+        if R != n_img * G:
+            raise ValueError(f"score: candidates_per_image = {G}: {n_img} images need {n_img * G} label rows (image-major: row r belongs "
+                             f"to image r // {G}), got {R}")
+        if T < 1 or T > int(mc.max_position_embeddings):
+            raise ValueError(f"score: T = {T} label positions, the decoder has max_position_embeddings = {mc.max_position_embeddings}")
+        mask = (lab != int(mc.pad_token_id)) if attention_mask is None else host(attention_mask)
+        if mask.shape != lab.shape or not np.isin(mask, (0, 1)).all():
+            raise ValueError(f"score: attention_mask must be 0/1 of the labels' shape {lab.shape}")
+        mask = mask.astype(np.int32)
+        valid = lab[mask != 0]
+        if valid.size and (valid.min() < 0 or valid.max() >= int(mc.vocab_size)):
+            raise ValueError(f"score: label ids on valid positions must lie in [0, {mc.vocab_size}), got [{int(valid.min())}, {int(valid.max())}]")
+        lab = np.where(mask != 0, lab, int(mc.pad_token_id))  # (a masked position carries no score; its id may be anything)
+        dec_in = shift_tokens_right(lab, int(mc.pad_token_id)) if decoder_input_ids is None else host(decoder_input_ids)
+        if dec_in.shape != lab.shape or not np.issubdtype(dec_in.dtype, np.integer) or dec_in.min() < 0 or dec_in.max() >= int(mc.vocab_size):
+            raise ValueError(f"score: decoder_input_ids must be ids in [0, {mc.vocab_size}) of the labels' shape {lab.shape}")
+        # ---- the device work
+        self._use_params(params)
+        px = self._dev(pixel_values, torch.float32)
+        self._check_pixels(px)
+        eng, dev = self.engine, self.device
+        ln = mask.sum(1).astype(np.int32)
+        idx, row_lab = loss_rows(mask, lab)
+        Mc = int(idx.size)
+        ll, tok = torch.zeros(R, dtype=torch.float32, device=dev), None
+        if return_token_logprobs:
+            tok = torch.zeros(R * T, dtype=torch.float32, device=dev)
+        if Mc == 0:
+            d_ln = torch.zeros(R, dtype=torch.int32, device=dev)
+        else:
+            off = np.zeros(R, dtype=np.int32)
+            off[1:] = np.cumsum(ln)[:-1]
+            images = n_img if G > 1 else None
+            compact = Mc < R * T
+            # packed rows: prefix masks, bf16 storage (and no empty row: a sequence of the packed attention has at least one query)
+            pk = packed_rows(mask, dec_in) if compact and eng.dt == torch.bfloat16 and ln.min() > 0 else None
+            # every integer array of the pass in ONE upload (no per-array synchronous copy between two calls)
+            up = [off, ln, idx, row_lab if compact else lab]
+            if pk is not None:
+                up += list(pk) + (list(group_packed_rows(pk[0], pk[1], G)) if G > 1 else [])
+            else:
+                up += [dec_in, mask]
+            d = self._upload_i32(up)
+            d_off, d_ln, d_idx, d_lab = d[:4]
+            rows = (d_idx, Mc) if compact else None
+            if pk is not None:
+                q_off, q_len, ids_p, pos_p = d[4:8]
+                t_lp, sums = eng.score_rows(px, ids_p, pos_p, None, d_lab, R, T, seg=(d_off, d_ln), rows=rows, row_labels=d_lab,
+                                            pack=(q_off, q_len, Mc) + tuple(d[8:]), images=images)
+            else:
+                pos = torch.arange(T, dtype=torch.int32, device=dev)[None].expand(R, T).contiguous()
+                t_lp, sums = eng.score_rows(px, d[4], pos.reshape(-1), d[5].view(R, T), d_lab, R, T, seg=(d_off, d_ln), rows=rows,
+                                            row_labels=d_lab, images=images)
+            ll.copy_(sums)
+            if tok is not None:
+                if rows is None:
+                    tok.copy_(t_lp)
+                else:
+                    tok.index_copy_(0, d_idx.long(), t_lp)
+        out = ModelOutput(log_likelihood=ll, num_tokens=d_ln.clone())
+        if tok is not None:
+            out["token_logprobs"] = tok.view(R, T)
+        return out
+
+    def _upload_i32(self, arrays):
+        """int32 device copies of the host integer arrays `arrays` (flattened), as views of ONE device buffer filled by ONE asynchronous
+        copy from a pinned staging buffer that only ever grows; every view starts at a multiple of 256 bytes.  The staging buffer is
+        rewritten only after the copy of the previous call has run (an event)."""
+        sizes = [(a.size + 63) // 64 * 64 for a in arrays]
+        total = sum(sizes)
+        host, ev = getattr(self, "_i32_stage", (None, None))
+        if host is None or host.numel() < total:
+            host, ev = torch.empty(max(total, 1 << 16), dtype=torch.int32).pin_memory(), None
+        if ev is not None:
+            ev.synchronize()
+        view, offs, o = host.numpy(), [], 0
+        for a, n in zip(arrays, sizes):
+            view[o: o + a.size] = np.asarray(a).reshape(-1)
+            offs.append(o)
+            o += n
+        d = torch.empty(total, dtype=torch.int32, device=self.device)
+        d.copy_(host[:total], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._i32_stage = (host, ev)
+        return [d[o: o + a.size] for o, a in zip(offs, arrays)]
+
     def _attention_weights(self, B: int, T: int, mask: torch.Tensor) -> dict:
         """`output_attentions=True` (modeling:499-510): the softmax weights of every attention of the pass that has just run with
         `save=True`, recomputed from the kept q / k projections by the diagnostic kernel `mic_attn_probs` (the fused attention cores

@@ -57,16 +57,19 @@ class pinned_stream:
         _STREAM_OVERRIDE = self.prev
 
 
-def gemm_args(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: int, K: int, *, a_kmajor=False, b_kmajor=False,
+def gemm_args(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor], M: int, N: int, K: int, *, a_kmajor=False, b_kmajor=False,
               bias=None, act=0, zout=None, zin=None, dact=0, residual=None, accumulate=False, dropout_p=0.0, dropout_seed=0,
               alpha=1.0, lda=None, ldb=None, ldc=None, ldz=None, ldr=None, split_k=0, split_stride=0, a_rowsum=None, rowsum_k=0,
               a_scale_inv=None, b_scale_inv=None, rowstat=None, rowstat_nvalid=0, ln_stats=None, ln_colsum=None, ln_width=0,
-              ln_eps=0.0, rowsum2=None, k_valid=0, c_q8=None) -> "L.GemmArgs":
+              ln_eps=0.0, rowsum2=None, k_valid=0, c_q8=None, pick_col=None, pick_out=None) -> "L.GemmArgs":
     """fp8 operands: `a` / `b` are torch.float8_e4m3fn / float8_e5m2 tensors (both k-contiguous, or both k-major: the weight-gradient
     form), `a_scale_inv` / `b_scale_inv` the device scalars their quantiser / producer wrote.  c_q8 = (state fp32 [2], amax_next or
-    None): `out` is an fp8 tensor the epilogue fills under that tensor's delayed scale (fused emission, see `fp8_out`)."""
+    None): `out` is an fp8 tensor the epilogue fills under that tensor's delayed scale (fused emission, see `fp8_out`).
+    pick_col int32 [M] / pick_out fp32 [M] (with rowstat): pick_out[m] = the value of (m, pick_col[m]) as stored; `out` may then be None —
+    the launch stores no C (mic_gemm_args.pick_col)."""
     g = L.GemmArgs()
-    g.dtype, g.c_dtype = _dt(a), _dt(out)
+    g.dtype = _dt(a)
+    g.c_dtype = _dt(out) if out is not None else g.dtype
     if g.dtype == L.MIC_FP8:
         g.a_fmt, g.b_fmt = _FP8[a.dtype], _FP8[b.dtype]
         g.a_scale_inv, g.b_scale_inv = _p(a_scale_inv), _p(b_scale_inv)
@@ -74,7 +77,7 @@ def gemm_args(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: in
     g.a_kmajor, g.b_kmajor = int(a_kmajor), int(b_kmajor)
     g.A, g.lda = _p(a), lda if lda is not None else a.stride(0)
     g.B, g.ldb = _p(b), ldb if ldb is not None else b.stride(0)
-    g.C, g.ldc = _p(out), ldc if ldc is not None else out.stride(0)
+    g.C, g.ldc = _p(out), ldc if ldc is not None else (out.stride(0) if out is not None else 0)
     g.bias, g.act = _p(bias), act
     zz = zout if zout is not None else zin
     g.Zout, g.Zin, g.dact = _p(zout), _p(zin), dact
@@ -89,6 +92,9 @@ def gemm_args(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: in
         g.a_ln_stats, g.a_ln_colsum, g.a_ln_width, g.a_ln_eps = _p(ln_stats), _p(ln_colsum), int(ln_width), float(ln_eps)
     g.rowsum2 = _p(rowsum2)  # int64 [M][2]: (sum, sum of squares) x 2^20 of the stored output rows, accumulated
     g.k_valid = int(k_valid)  # k-major x k-major launches: operand rows k >= k_valid count as zero (0 = all)
+    if pick_col is not None and pick_col.dtype != torch.int32 or pick_out is not None and pick_out.dtype != torch.float32:
+        raise L.MicError("pick_col is int32, pick_out is float32")
+    g.pick_col, g.pick_out = _p(pick_col), _p(pick_out)
     if c_q8 is not None:
         if g.c_dtype != L.MIC_FP8:
             raise L.MicError("c_q8 goes with an fp8 output tensor")
@@ -96,8 +102,9 @@ def gemm_args(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: in
     return g
 
 
-def gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: int, K: int, **kw):
-    """out[M,N] = epi(op(a) @ op(b)); a: [M,K] (or [K,M] if a_kmajor); b: [N,K] (or [K,N] if b_kmajor)."""
+def gemm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor], M: int, N: int, K: int, **kw):
+    """out[M,N] = epi(op(a) @ op(b)); a: [M,K] (or [K,M] if a_kmajor); b: [N,K] (or [K,N] if b_kmajor).  out=None: a pick launch
+    that stores no C (gemm_args)."""
     g = gemm_args(a, b, out, M, N, K, **kw)
     L.check(L.lib().mic_gemm(C.byref(g), _stream()), "mic_gemm")
     return out
@@ -118,14 +125,21 @@ def get_cu_budget() -> int:
     return int(L.lib().mic_get_cu_budget())
 
 
-def gemm_plan(shapes, *, a_kmajor=False, b_kmajor=False, split_k=0, dtype=None, kernel=False) -> dict:
+def gemm_plan(shapes, *, a_kmajor=False, b_kmajor=False, split_k=0, dtype=None, kernel=False, rowstat=False, pick=False) -> dict:
     """What the planner would launch for the problems [(M, N, K), ...] of one grouped bf16 launch under the current CU budget
     (host arithmetic; nothing runs and no device memory is needed).  kernel=True: also which kernel runs ("family": an index into
-    _lib.GEMM_FAMILIES, "plain", "epi": include/mic_hip.h)."""
+    _lib.GEMM_FAMILIES, "plain", "epi": include/mic_hip.h).  rowstat=True: the problems carry softmax partials (the LM head);
+    pick=True: ... and picked values without a C (the scorer's head, gemm_args pick_col / pick_out) — the planner looks at which
+    by-products a launch has, never at their addresses, so the marks are placeholder non-null values."""
     arr = (L.GemmArgs * len(shapes))()
     for g, (M, N, K) in zip(arr, shapes):
         g.dtype = g.c_dtype = L.MIC_BF16 if dtype is None else dtype
         g.M, g.N, g.K, g.a_kmajor, g.b_kmajor, g.split_k = M, N, K, int(a_kmajor), int(b_kmajor), int(split_k)
+        if rowstat or pick:
+            g.rowstat, g.rowstat_ld, g.rowstat_nvalid = 64, (N + 63) // 64, N
+            g.lda = g.ldb = K  # (dense operands: the 2^31-byte operand window of families 5 / 6 is part of the answer)
+        if pick:
+            g.pick_col = g.pick_out = 64
     out = L.GemmPlanInfo()
     L.check(L.lib().mic_gemm_plan(arr, len(shapes), C.byref(out)), "mic_gemm_plan")
     return {k: getattr(out, k) for k, _ in L.GemmPlanInfo._fields_ if kernel or k not in ("family", "plain", "epi")}
@@ -358,6 +372,17 @@ def embed_rows_add_det(ids, dh, scale, dtable, n, width, ws):
     """dtable[ids[i]] += scale * dh[i] over the n rows, deterministically (ids < 0 skipped): the data-parallel embedding-row exchange"""
     L.check(L.lib().mic_embed_rows_add_det(_dt(dh), int(n), int(width), int(dtable.shape[0]) if dtable.dim() == 2 else int(dtable.numel() // width),
                                            _p(ids), _p(dh), float(scale), _p(dtable), _p(ws), _stream()), "mic_embed_rows_add_det")
+
+
+def ce_rows_picked(V, rowstat, label_logit, row_lse, row_loss, rows):
+    """ce_rows_tiles with the label's logit from `label_logit` fp32 [rows] (the pick_out of a head launch without logits)"""
+    L.check(L.lib().mic_ce_rows_picked(rows, V, _p(rowstat), rowstat.stride(0) // 2, _p(label_logit), _p(row_lse), _p(row_loss), _stream()),
+            "mic_ce_rows_picked")
+
+
+def segment_sums(seg_off, seg_len, x, out, n_seg, scale=1.0):
+    """out[s] = scale * sum(x[seg_off[s] : seg_off[s] + seg_len[s]]) (fp32; int32 offsets / lengths), fixed summation order"""
+    L.check(L.lib().mic_segment_sums(n_seg, _p(seg_off), _p(seg_len), _p(x), float(scale), _p(out), _stream()), "mic_segment_sums")
 
 
 def ce_rows(logits, ld, V, labels, mask, ls, row_lse, row_loss, rows):

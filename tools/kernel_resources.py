@@ -5,7 +5,8 @@ Makefile leaves in csrc/build/<unit>.res): VGPRs / AGPRs / SGPRs, scratch, spill
   python tools/kernel_resources.py --update   rewrite tests/golden/kernel_resources.json from the current build (and
                                               tests/golden/kernel_resources_units.json from csrc/build/units/: the Makefile's UNIT_SRCS;
                                               tests/golden/kernel_resources_units_inc.json from csrc/build/units_inc/: INC_UNIT_SRCS;
-                                              tests/golden/kernel_resources_units_tile.json from csrc/build/units_tile/: TILE_UNIT_SRCS)
+                                              tests/golden/kernel_resources_units_tile.json from csrc/build/units_tile/: TILE_UNIT_SRCS;
+                                              tests/golden/kernel_resources_units_score.json from csrc/build/units_score/: SCORE_UNIT_SRCS)
 
 The guard (tests/test_kernel_resources_cpu.py) fails on scratch or spills in any kernel, on an occupancy below the committed one, and
 on kernels the table does not know — the two silent regressions of round 4 (272 B of scratch in the non-PLAIN 256x256 epilogues, a
@@ -28,6 +29,9 @@ INC_UNITS_TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources_units_
 # ... and the units of that kind built from the attention cores' tile text (TILE_UNIT_SRCS), under build/units_tile/
 TILE_UNITS_BUILD = os.path.join(BUILD, "units_tile")
 TILE_UNITS_TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources_units_tile.json")
+# ... and the units behind model.score (SCORE_UNIT_SRCS: gemm_d2_kernel<2> on gemm_d2.hip's text, the picked-logit CE and segment sums)
+SCORE_UNITS_BUILD = os.path.join(BUILD, "units_score")
+SCORE_UNITS_TABLE = os.path.join(ROOT, "tests", "golden", "kernel_resources_units_score.json")
 FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
           "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
 
@@ -106,16 +110,17 @@ def compare(cur, ref):
 
 def main():
     cur, cur_units, cur_inc, cur_tile = current(), current(UNITS_BUILD), current(INC_UNITS_BUILD), current(TILE_UNITS_BUILD)
+    cur_score = current(SCORE_UNITS_BUILD)
     if not cur:
         sys.exit(f"no .res files under {BUILD}: build first (make -C multilingual-image-captioning_amd/csrc)")
     if "--update" in sys.argv:
         os.makedirs(os.path.dirname(TABLE), exist_ok=True)
-        for table, c in ((TABLE, cur), (UNITS_TABLE, cur_units), (INC_UNITS_TABLE, cur_inc), (TILE_UNITS_TABLE, cur_tile)):
+        for table, c in ((TABLE, cur), (UNITS_TABLE, cur_units), (INC_UNITS_TABLE, cur_inc), (TILE_UNITS_TABLE, cur_tile), (SCORE_UNITS_TABLE, cur_score)):
             json.dump(c, open(table, "w"), indent=0, sort_keys=True)
             print(f"wrote {table}: {sum(len(v) for v in c.values())} kernels in {len(c)} units")
         return
     print(f"{'unit':<12} {'kernel':<88} {'vgpr':>4} {'agpr':>4} {'sgpr':>4} {'scr':>4} {'occ':>3} {'lds':>6}")
-    for table, c in ((TABLE, cur), (UNITS_TABLE, cur_units), (INC_UNITS_TABLE, cur_inc), (TILE_UNITS_TABLE, cur_tile)):
+    for table, c in ((TABLE, cur), (UNITS_TABLE, cur_units), (INC_UNITS_TABLE, cur_inc), (TILE_UNITS_TABLE, cur_tile), (SCORE_UNITS_TABLE, cur_score)):
         ref = json.load(open(table)) if os.path.exists(table) else {}
         for unit, ks in c.items():
             for name, v in sorted(ks.items()):
