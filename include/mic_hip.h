@@ -431,6 +431,24 @@ int mic_ce_reduce(int rows, const float* row_loss, const int32_t* mask, float* l
 int mic_ce_bwd(int dtype, int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels,
                const int32_t* mask, float label_smoothing, const float* row_lse, const float* denom,
                float loss_scale, void* stream);
+/* Per-row loss weights (reward-weighted likelihood: loss = sum_r weight[r] mask[r] row_loss[r] / sum_r mask[r]).  The _w forms take
+ * row_weight, one fp32 per head row — any finite value, zeros and negatives included; NULL: the unweighted function, launch for launch
+ * and bit for bit (the unweighted entry points call these with NULL: one kernel text).  Refusals are those of the unweighted functions.
+ *   mic_ce_reduce_w: loss_out = sum row_loss[r] * (mask[r] * row_weight[r]) / sum mask[r]; denom_out is the exact mask count — it does
+ *     not depend on the weights (a row of weight 0 still counts there; the mask drops a row).  As in mic_ce_reduce, a row that
+ *     contributes nothing — mask 0, and here also weight 0 — must have a finite row_loss (0 * inf is NaN).
+ *   mic_ce_bwd_w (bf16 / fp32 logits), mic_ce_bwd_t_w (bf16; transposed copy and colsum as mic_ce_bwd_t): the row factor is
+ *     mask[row] ? (loss_scale / denom[0]) * row_weight[row] : 0, the products in that order, so all weights 1.0 give the bits of the
+ *     unweighted call.  A row whose factor is zero (mask 0, weight +0, weight -0) is +0 bits everywhere, like a masked row; padding
+ *     columns V .. Vpad are +0.  colsum adds the stored (weighted) dlogits.  row_weight[row] is read for row < rows only.
+ *   mic_ce_bwd_q8 has no weighted form: its closed-form scale rests on |g| <= 1. */
+int mic_ce_reduce_w(int rows, const float* row_loss, const int32_t* mask, const float* row_weight, float* loss_out, float* denom_out,
+                    void* stream);
+int mic_ce_bwd_w(int dtype, int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels, const int32_t* mask,
+                 const float* row_weight, float label_smoothing, const float* row_lse, const float* denom, float loss_scale, void* stream);
+int mic_ce_bwd_t_w(int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels, const int32_t* mask, const float* row_weight,
+                   float label_smoothing, const float* row_lse, const float* denom, float loss_scale, void* dlogits_t, int ld_t,
+                   int rows_pad, float* colsum, void* stream);
 /* mic_ce_bwd (bf16 logits) with the gradient leaving as fp8 bytes q8->q [rows][ldq] (e5m2) instead of in place — the logits stay as they
  * are.  The scale of this tensor is known in closed form: every entry of g = mask (softmax - soft_label) lies in [-1, 1], so q = fp8(g *
  * FMAX) and the dequantisation factor q8->state[1] = loss_scale / (denom * FMAX) (state[0] = its reciprocal) are written with no amax

@@ -489,31 +489,47 @@ extern "C" int mic_ce_rows_tiles(int dtype, int rows, int V, const void* logits,
     hipLaunchKernelGGL(ce_rows_tiles_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, rows, (const T*)logits, ld, (const float2*)rowstat, stat_ld, ntiles, labels, row_lse, row_loss);
   });
 }
+// row_weight != NULL (mic_ce_reduce_w): row r counts mask * row_weight[r] in the loss; the denominator stays the mask count
 __global__ __launch_bounds__(256) void ce_reduce_kernel(int rows, const float* __restrict__ row_loss,
-                                                        const int32_t* __restrict__ mask, float* loss_out, float* denom_out) {
+                                                        const int32_t* __restrict__ mask, const float* __restrict__ row_weight,
+                                                        float* loss_out, float* denom_out) {
   __shared__ float sl[256], sd[256];
   float l = 0.f, d = 0.f;
-  for (int r = threadIdx.x; r < rows; r += 256) { const float mk = (float)mask[r]; l += row_loss[r] * mk; d += mk; }
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const float mk = (float)mask[r];
+    l += row_loss[r] * (row_weight ? mk * row_weight[r] : mk);
+    d += mk;
+  }
   sl[threadIdx.x] = l; sd[threadIdx.x] = d;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) { sl[threadIdx.x] += sl[threadIdx.x + o]; sd[threadIdx.x] += sd[threadIdx.x + o]; } __syncthreads(); }
   if (threadIdx.x == 0) { denom_out[0] = sd[0]; loss_out[0] = sl[0] / sd[0]; }
 }
-extern "C" int mic_ce_reduce(int rows, const float* row_loss, const int32_t* mask, float* loss_out, float* denom_out, void* stream) {
+extern "C" int mic_ce_reduce_w(int rows, const float* row_loss, const int32_t* mask, const float* row_weight, float* loss_out,
+                               float* denom_out, void* stream) {
   MIC_CHECK(rows > 0 && row_loss && mask && loss_out && denom_out, "mic_ce_reduce: bad args");
-  hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, row_loss, mask, loss_out, denom_out);
+  hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, row_loss, mask, row_weight, loss_out, denom_out);
   MIC_LAUNCH_CHECK();
   return MIC_OK;
 }
+extern "C" int mic_ce_reduce(int rows, const float* row_loss, const int32_t* mask, float* loss_out, float* denom_out, void* stream) {
+  return mic_ce_reduce_w(rows, row_loss, mask, nullptr, loss_out, denom_out, stream);
+}
 // dlogits = mask/denom * loss_scale * (softmax - soft_label); soft_label = conf at label, low elsewhere.
+// The row factor with a per-row loss weight (mic_ce_bwd_w / mic_ce_bwd_t_w; NULL: none): (loss_scale / denom) * row_weight[row], in
+// that order — a weight of 1.0 leaves the bits as they are, a weight of +0 or -0 makes the row a masked one (+0 everywhere).
+__device__ __forceinline__ float ce_row_factor(int masked_in, float inv_denom, const float* __restrict__ row_weight, int row) {
+  if (!masked_in) return 0.f;
+  return row_weight ? inv_denom * row_weight[row] : inv_denom;
+}
 template <typename T>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(int V, int Vpad, T* __restrict__ logits, int ld,
                                                      const int32_t* __restrict__ labels, const int32_t* __restrict__ mask,
                                                      float ls, const float* __restrict__ row_lse, const float* __restrict__ denom,
-                                                     float loss_scale) {
+                                                     float loss_scale, const float* __restrict__ row_weight) {
   const int row = blockIdx.x;
   T* lr = logits + (size_t)row * ld;
-  const float w = mask[row] ? loss_scale / denom[0] : 0.f;
+  const float w = ce_row_factor(mask[row], loss_scale / denom[0], row_weight, row);
   const float lse = row_lse[row];
   const int label = labels[row];
   const float conf = 1.0f - ls, low = ls > 0.f ? ls / (float)(V - 1) : 0.f;
@@ -538,14 +554,19 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(int V, int Vpad, T* __restr
     }
   }
 }
-extern "C" int mic_ce_bwd(int dtype, int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels,
-                          const int32_t* mask, float label_smoothing, const float* row_lse, const float* denom,
-                          float loss_scale, void* stream) {
+extern "C" int mic_ce_bwd_w(int dtype, int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels,
+                            const int32_t* mask, const float* row_weight, float label_smoothing, const float* row_lse,
+                            const float* denom, float loss_scale, void* stream) {
   MIC_CHECK(rows > 0 && V > 1 && Vpad >= V && Vpad % 8 == 0 && ld >= Vpad && logits && labels && mask && row_lse && denom, "mic_ce_bwd: bad args");
   return dispatch_t(dtype, [&](auto* tag) {
     using T = TYPE_OF(tag);
-    hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(rows), dim3(256), 0, (hipStream_t)stream, V, Vpad, (T*)logits, ld, labels, mask, label_smoothing, row_lse, denom, loss_scale);
+    hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(rows), dim3(256), 0, (hipStream_t)stream, V, Vpad, (T*)logits, ld, labels, mask, label_smoothing, row_lse, denom, loss_scale, row_weight);
   });
+}
+extern "C" int mic_ce_bwd(int dtype, int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels,
+                          const int32_t* mask, float label_smoothing, const float* row_lse, const float* denom,
+                          float loss_scale, void* stream) {
+  return mic_ce_bwd_w(dtype, rows, V, Vpad, logits, ld, labels, mask, nullptr, label_smoothing, row_lse, denom, loss_scale, stream);
 }
 
 // ------------------------------------------------------------------ 64 x 512 tile transpose (bf16), optionally behind the CE backward
@@ -566,6 +587,7 @@ struct TransposeArgs {
   int rows, cols;
   // CE backward (OP = 1): see ce_bwd_kernel
   int V; const int32_t* labels; const int32_t* mask; float ls; const float* row_lse; const float* denom; float loss_scale;
+  const float* row_weight;  // per-row loss weight [rows] (mic_ce_bwd_t_w), or NULL
   float* colsum;  // += column sums of the stored dlogits (fp32 atomics; the final_logits_bias gradient), or NULL
 };
 template <int OP>
@@ -590,7 +612,7 @@ __global__ __launch_bounds__(256) void tile_transpose_kernel(TransposeArgs a) {
     uint4 u = q[rr];
     if constexpr (OP == 1) {
       if (row < a.rows && col_ok) {
-        const float w = a.mask[row] ? inv_denom : 0.f;
+        const float w = ce_row_factor(a.mask[row], inv_denom, a.row_weight, row);
         const float lse = a.row_lse[row];
         const int label = a.labels[row];
         const float conf = 1.0f - a.ls, low = a.ls > 0.f ? a.ls / (float)(a.V - 1) : 0.f;
@@ -653,9 +675,9 @@ extern "C" int mic_transpose_bf16(int rows, int rows_pad, int cols, const void* 
 }
 // mic_ce_bwd (bf16) that ALSO writes dlogits^T [Vpad][ld_t] (columns rows .. rows_pad zero) and, when `colsum` is
 // given, adds the column sums of the stored dlogits to it (the final_logits_bias gradient, main.py:178's parameter)
-extern "C" int mic_ce_bwd_t(int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels, const int32_t* mask,
-                            float label_smoothing, const float* row_lse, const float* denom, float loss_scale, void* dlogits_t,
-                            int ld_t, int rows_pad, float* colsum, void* stream) {
+extern "C" int mic_ce_bwd_t_w(int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels, const int32_t* mask,
+                              const float* row_weight, float label_smoothing, const float* row_lse, const float* denom, float loss_scale,
+                              void* dlogits_t, int ld_t, int rows_pad, float* colsum, void* stream) {
   if (rows_pad <= 0) rows_pad = (rows + 63) / 64 * 64;
   MIC_CHECK(rows_pad >= rows && rows_pad % 64 == 0, "mic_ce_bwd_t: rows_pad >= rows, a multiple of 64");
   MIC_CHECK(rows > 0 && V > 1 && Vpad >= V && Vpad % 8 == 0 && ld >= Vpad && ld % 8 == 0 && logits && labels && mask && row_lse && denom && dlogits_t,
@@ -665,10 +687,16 @@ extern "C" int mic_ce_bwd_t(int rows, int V, int Vpad, void* logits, int ld, con
   TransposeArgs a{};
   a.src = (const uint16_t*)logits; a.src_rw = (uint16_t*)logits; a.ld_src = ld; a.dst = (uint16_t*)dlogits_t; a.ld_dst = ld_t;
   a.rows = rows; a.cols = Vpad; a.V = V; a.labels = labels; a.mask = mask; a.ls = label_smoothing; a.row_lse = row_lse; a.denom = denom;
-  a.loss_scale = loss_scale; a.colsum = colsum;
+  a.loss_scale = loss_scale; a.colsum = colsum; a.row_weight = row_weight;
   hipLaunchKernelGGL(tile_transpose_kernel<1>, dim3((Vpad + 511) / 512, rows_pad / 64), dim3(256), 0, (hipStream_t)stream, a);
   MIC_LAUNCH_CHECK();
   return MIC_OK;
+}
+extern "C" int mic_ce_bwd_t(int rows, int V, int Vpad, void* logits, int ld, const int32_t* labels, const int32_t* mask,
+                            float label_smoothing, const float* row_lse, const float* denom, float loss_scale, void* dlogits_t,
+                            int ld_t, int rows_pad, float* colsum, void* stream) {
+  return mic_ce_bwd_t_w(rows, V, Vpad, logits, ld, labels, mask, nullptr, label_smoothing, row_lse, denom, loss_scale, dlogits_t, ld_t,
+                        rows_pad, colsum, stream);
 }
 
 // ------------------------------------------------------------------ CE backward with the gradient leaving as e5m2 bytes (fp8 LM head)

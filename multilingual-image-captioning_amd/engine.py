@@ -1086,15 +1086,22 @@ class Engine(Fp8Views):
         return dehs
 
     # ------------------------------------------------------------------ loss (main.py:658-680) on materialised logits
-    def loss_and_dlogits(self, logits, labels, mask, M: int, label_smoothing: float, backward: bool, stat=None):
+    def loss_and_dlogits(self, logits, labels, mask, M: int, label_smoothing: float, backward: bool, stat=None, row_weights=None):
+        """row_weights (fp32 device vector, one per head row; None: the plain loss): loss = sum w mask row_loss / sum mask, and the
+        weight enters dlogits through the row factor (mic_ce_reduce_w / mic_ce_bwd_w / mic_ce_bwd_t_w) — everything behind the
+        cross-entropy is linear in it.  Refused with fp8 GEMMs (mic_ce_bwd_q8's closed-form scale rests on |g| <= 1)."""
         P = self.P
+        self._check_row_weights(row_weights, M)
         lse, rl = self.vec("ce.lse", _rup(M, ROWPAD)), self.vec("ce.rowloss", _rup(M, ROWPAD))
         loss, denom = self.vec("ce.loss", 1), self.vec("ce.denom", 1)
         if stat is not None and label_smoothing == 0.0:
             ops.ce_rows_tiles(logits, logits.stride(0), P.V, stat, labels, lse, rl, M)  # lse from the head GEMM's tile partials
         else:
             ops.ce_rows(logits, logits.stride(0), P.V, labels, mask, label_smoothing, lse, rl, M)
-        ops.ce_reduce(rl, mask, loss, denom, M)
+        if row_weights is None:
+            ops.ce_reduce(rl, mask, loss, denom, M)
+        else:
+            ops.ce_reduce(rl, mask, loss, denom, M, row_weight=row_weights)
         if backward and self._head8():
             # fp8 head: dlogits leave as ONE e5m2 copy (the logits stay) under the scale this tensor has in closed form (mic_ce_bwd_q8)
             ops.zero(P.g("flb"))
@@ -1114,12 +1121,31 @@ class Engine(Fp8Views):
                 Kp = _rup(M, 128)
                 dT = self.buf("d.dlogitsT", P.Vpad, kcap)
                 ops.zero(P.g("flb"))
-                ops.ce_bwd_t(logits, logits.stride(0), P.V, P.Vpad, labels, mask, label_smoothing, lse, denom, M, dT, rows_pad=Kp, colsum=P.g("flb"))
+                if row_weights is None:
+                    ops.ce_bwd_t(logits, logits.stride(0), P.V, P.Vpad, labels, mask, label_smoothing, lse, denom, M, dT, rows_pad=Kp, colsum=P.g("flb"))
+                else:
+                    ops.ce_bwd_t(logits, logits.stride(0), P.V, P.Vpad, labels, mask, label_smoothing, lse, denom, M, dT, rows_pad=Kp, colsum=P.g("flb"),
+                                 row_weight=row_weights)
                 self._head_nt_state = (dT, Kp)
             else:
-                ops.ce_bwd(logits, logits.stride(0), P.V, P.Vpad, labels, mask, label_smoothing, lse, denom, M)
+                if row_weights is None:
+                    ops.ce_bwd(logits, logits.stride(0), P.V, P.Vpad, labels, mask, label_smoothing, lse, denom, M)
+                else:
+                    ops.ce_bwd(logits, logits.stride(0), P.V, P.Vpad, labels, mask, label_smoothing, lse, denom, M, row_weight=row_weights)
                 self._head_nt_state = None
         return loss
+
+    def _check_row_weights(self, row_weights, n: int):
+        """per-row loss weights of a pass whose head has `n` rows: checked before anything is launched (None: nothing to check)"""
+        if row_weights is None:
+            return
+        if self.fp8:
+            raise ValueError("row_weights are not supported together with fp8 GEMMs (out of scope: the e5m2 dlogits of mic_ce_bwd_q8 "
+                             "carry a closed-form scale that rests on |g| <= 1)")
+        if (not isinstance(row_weights, torch.Tensor) or row_weights.dtype != torch.float32 or row_weights.dim() != 1
+                or row_weights.numel() != n or not row_weights.is_contiguous() or row_weights.device.type != self.dev.type):
+            raise ValueError(f"row_weights: a contiguous float32 vector of {n} elements on {self.dev} (one per head row), got "
+                             f"{getattr(row_weights, 'dtype', type(row_weights))} {tuple(getattr(row_weights, 'shape', ()))}")
 
     def _head_nt_kcap(self, logits) -> int:
         """columns of the dlogits^T buffer (the capacity of the row dimension, a multiple of 128) when the head's backward runs as NT
@@ -1197,19 +1223,22 @@ class Engine(Fp8Views):
         return logits, stat
 
     def loss_only(self, pixels, ids, pos_ids, key_mask, labels, B, T, *, label_smoothing=0.0, rows=None, row_labels=None, pack=None,
-                  images=None):
-        """eval_step's forward + loss (main.py:710-716).  images: see loss_and_grads."""
+                  images=None, row_weights=None):
+        """eval_step's forward + loss (main.py:710-716).  images, row_weights: see loss_and_grads."""
         M = B * T
         pack = self._check_pack(pack, rows, T)
         self._check_images(pixels, B, images, pack)
+        self._check_row_weights(row_weights, M if rows is None else rows[1])
         if rows is None:
             logits, _, stat = self.forward_logits(pixels, ids, pos_ids, key_mask, B, T, save=False, seed=None, stats=True, images=images)
-            return self.loss_and_dlogits(logits, labels, key_mask.reshape(-1), M, label_smoothing, backward=False, stat=stat)
+            return self.loss_and_dlogits(logits, labels, key_mask.reshape(-1), M, label_smoothing, backward=False, stat=stat,
+                                         row_weights=row_weights)
         self._fp8_begin_pass()
         _, ehs = self.vit_forward(pixels, False)
         hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, False, None, pack=pack, images=images)
         logits, stat = self.compact_head(hf, M, rows, packed=pack is not None)
-        return self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=False, stat=stat)
+        return self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=False, stat=stat,
+                                     row_weights=row_weights)
 
     # ------------------------------------------------------------------ teacher-forced scores (model.score)
     SCORE_CHUNK_ROWS = 4096  # materialised scoring head: rows per chunk — its logits never exceed loss_only's buffer for that many rows
@@ -1298,28 +1327,35 @@ class Engine(Fp8Views):
         return t[:n]
 
     def loss_and_grads(self, pixels, ids, pos_ids, key_mask, labels, B, T, *, label_smoothing=0.0, seed=None, rows=None,
-                       row_labels=None, pack=None, images=None):
+                       row_labels=None, pack=None, images=None, row_weights=None):
         """value_and_grad(compute_loss) of train_step (main.py:688-697): grads land in ParamStore.grad.
         rows = (idx int32 [Mc] of the positions with loss mask 1, Mc) and row_labels = labels[idx] switch the LM head,
         the cross-entropy and their backward to those rows only (identical loss and gradients, ~(1 - Mc/M) less head work).
         images (None = B): the number of distinct images in `pixels` — G = B // images captions per image, caption row r belongs to
         image r // G.  The step is the one on pixels.repeat_interleave(G, 0): the image tower, the cross k/v projections and their
-        backward run at images*S rows, an image's encoder states receive the sum of its captions' gradients."""
+        backward run at images*S rows, an image's encoder states receive the sum of its captions' gradients.
+        row_weights (None: the plain loss): fp32 device vector over the head's rows — the `rows` positions when the head is compacted,
+        else all B*T — of per-row loss weights w: loss = sum w mask l / sum mask (the denominator does not depend on w; any finite
+        value, zeros and negatives included), gradients those of that loss.  All weights 1.0 give the plain step's bits.  ValueError
+        before any launch with fp8 GEMMs."""
         P = self.P
         self._check_images(pixels, B, images, None if pack is None else self._check_pack(pack, rows, T))
+        self._check_row_weights(row_weights, B * T if rows is None else rows[1])
         P.ensure_grads()
         ops.zero(P.grad[P.atomic_begin:])
         M = B * T
         pack = self._check_pack(pack, rows, T)
         if rows is None:
             logits, ehs, stat = self.forward_logits(pixels, ids, pos_ids, key_mask, B, T, save=True, seed=seed, stats=True, images=images)
-            loss = self.loss_and_dlogits(logits, labels, key_mask.reshape(-1), M, label_smoothing, backward=True, stat=stat)
+            loss = self.loss_and_dlogits(logits, labels, key_mask.reshape(-1), M, label_smoothing, backward=True, stat=stat,
+                                         row_weights=row_weights)
         else:
             self._fp8_begin_pass()
             _, ehs = self.vit_forward(pixels, True)
             hf = self.decoder_forward(ids, pos_ids, key_mask, ehs, B, T, True, seed, pack=pack, images=images)
             logits, stat = self.compact_head(hf, M, rows, packed=pack is not None)
-            loss = self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=True, stat=stat)
+            loss = self.loss_and_dlogits(logits, row_labels, self.ones_i32(rows[1]), rows[1], label_smoothing, backward=True, stat=stat,
+                                         row_weights=row_weights)
         dehs = self.decoder_backward(B, T, ids, pos_ids, key_mask, ehs, logits, seed, rows=rows, pack=pack, images=images)
         n_img = B if images is None else images
         if self.skip_vit_backward:

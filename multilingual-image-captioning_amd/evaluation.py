@@ -178,3 +178,62 @@ def rerank(model, pixel_values, sequences, n_per_image: int, length_penalty: flo
     dec_in, labels, mask = sequences_to_score_inputs(sequences, mc.eos_token_id, mc.pad_token_id)
     out = model.score(pixel_values, labels, mask, decoder_input_ids=dec_in, candidates_per_image=int(n_per_image))
     return rerank_scores(out["log_likelihood"].cpu().numpy(), out["num_tokens"].cpu().numpy(), n_per_image, length_penalty)
+
+
+def scst_advantages(rewards, n_per_image: int, baseline="mean_others"):
+    """Self-critical advantages of `n_per_image` sampled captions per image: rewards [images * n] (image-major: row image * n + j) ->
+    float32 advantages [images * n] = reward - baseline.  baseline: "mean_others" — the mean reward of the image's OTHER n - 1 samples
+    (unbiased: a sample's baseline does not depend on the sample; n = 1 has no others: ValueError) —, "mean" — the image's mean
+    reward —, or an array [images] of explicit baselines, e.g. the reward of each image's greedy caption.  Pure host function."""
+    r = np.asarray(rewards, dtype=np.float64).reshape(-1)
+    n = int(n_per_image)
+    if n < 1 or r.size % n:
+        raise ValueError(f"scst_advantages: {r.size} rewards do not divide into groups of {n_per_image}")
+    g = r.reshape(-1, n)
+    if isinstance(baseline, str):
+        if baseline == "mean_others":
+            if n == 1:
+                raise ValueError("scst_advantages: baseline='mean_others' needs n_per_image >= 2 (one sample has no others)")
+            b = (g.sum(1, keepdims=True) - g) / (n - 1)
+        elif baseline == "mean":
+            b = g.mean(1, keepdims=True)
+        else:
+            raise ValueError(f"scst_advantages: baseline={baseline!r}: expected 'mean_others', 'mean' or an array [images]")
+    else:
+        b = np.asarray(baseline, dtype=np.float64)
+        if b.shape != (g.shape[0],):
+            raise ValueError(f"scst_advantages: an explicit baseline has one entry per image [{g.shape[0]}], got {list(b.shape)}")
+        b = b[:, None]
+    return (g - b).reshape(-1).astype(np.float32)
+
+
+def self_critical_batch(model, pixel_values, reward_fn, n_samples: int, prng_key, max_length: int = 64, baseline="mean_others",
+                        **generate_kwargs):
+    """One batch of self-critical sequence training (the policy-gradient loss -(r - b) log p(sample)):
+      1. `model.generate(pixel_values, do_sample=True, num_return_sequences=n_samples, prng_key=prng_key, max_length=max_length,
+         num_beams=1, **generate_kwargs)` draws n_samples captions per image in one chain (rows image-major),
+      2. `sequences_to_score_inputs` turns them into decoder inputs, labels and the mask up to each caption's end,
+      3. `reward_fn(sequences)` — int ndarray [R, L], the rows as `generate` returned them — gives rewards [R]: the caller's metric on
+         the caller's terms (nothing is tokenised or decoded here),
+      4. `scst_advantages(rewards, n_samples, baseline)`.
+    Returns (batch, rewards float32 [R]); `batch` goes to `Trainer.train_step` as it is: pixel_values, input_ids (the labels),
+    attention_mask, decoder_input_ids, captions_per_image = n_samples, loss_weights.
+    The sign.  The train step MINIMISES sum_r w[r] sum_t m[r,t] nll[r,t] / sum m with nll = -log p.  The self-critical loss
+    -(r - b) log p(sample) is (r - b) * nll, so loss_weights = +advantage: a sample that beat its baseline has a positive weight on
+    its nll, descent lowers that nll — its likelihood rises — and a sample below its baseline has a negative weight and is pushed
+    away from.  (-advantage is the coefficient of log p, not of the per-token loss the weights multiply.)"""
+    n = int(n_samples)
+    generate_kwargs.setdefault("num_beams", 1)  # sampling is one beam per draw (a config default of several beams would refuse do_sample)
+    gen = model.generate(pixel_values, do_sample=True, num_return_sequences=n, prng_key=prng_key, max_length=max_length, **generate_kwargs)
+    seq = gen.sequences
+    seq = np.asarray(seq.cpu() if hasattr(seq, "cpu") else seq)
+    mc = model.config.mbart_config
+    dec_in, labels, mask = sequences_to_score_inputs(seq, mc.eos_token_id, mc.pad_token_id)
+    rewards = np.asarray(reward_fn(seq), dtype=np.float32).reshape(-1)
+    if rewards.shape != (seq.shape[0],):
+        raise ValueError(f"self_critical_batch: reward_fn returned {rewards.size} rewards for {seq.shape[0]} sampled captions")
+    if not np.isfinite(rewards).all():
+        raise ValueError("self_critical_batch: reward_fn returned non-finite rewards")
+    batch = {"pixel_values": pixel_values, "input_ids": labels, "attention_mask": mask, "decoder_input_ids": dec_in,
+             "captions_per_image": n, "loss_weights": scst_advantages(rewards, n, baseline)}
+    return batch, rewards

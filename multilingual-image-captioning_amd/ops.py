@@ -406,11 +406,28 @@ def row_topk_tiles(logits, ld, V, rowstat, k, top_val, top_idx, R, *, suppress_e
                                        eos_token_id, int(raw_logits), _p(row_bias), _p(top_val), _p(top_idx), _stream()), "mic_row_topk_tiles")
 
 
-def ce_reduce(row_loss, mask, loss_out, denom_out, rows):
+def _row_weight(row_weight, rows):
+    """the per-row loss weights of the weighted cross-entropy entry points: fp32, contiguous, one per head row"""
+    if row_weight.dtype != torch.float32 or not row_weight.is_contiguous() or row_weight.numel() < rows:
+        raise ValueError(f"row_weight: a contiguous float32 vector of at least {rows} elements, got {row_weight.dtype} {tuple(row_weight.shape)}")
+    return _p(row_weight)
+
+
+def ce_reduce(row_loss, mask, loss_out, denom_out, rows, row_weight=None):
+    """row_weight fp32 [rows]: loss = sum row_loss * (mask * row_weight) / sum mask (mic_ce_reduce_w)"""
+    if row_weight is not None:
+        L.check(L.lib().mic_ce_reduce_w(rows, _p(row_loss), _p(mask), _row_weight(row_weight, rows), _p(loss_out), _p(denom_out), _stream()),
+                "mic_ce_reduce_w")
+        return
     L.check(L.lib().mic_ce_reduce(rows, _p(row_loss), _p(mask), _p(loss_out), _p(denom_out), _stream()), "mic_ce_reduce")
 
 
-def ce_bwd(logits, ld, V, Vpad, labels, mask, ls, row_lse, denom, rows, loss_scale=1.0):
+def ce_bwd(logits, ld, V, Vpad, labels, mask, ls, row_lse, denom, rows, loss_scale=1.0, row_weight=None):
+    """row_weight fp32 [rows]: the row factor becomes mask ? (loss_scale / denom) * row_weight : 0 (mic_ce_bwd_w)"""
+    if row_weight is not None:
+        L.check(L.lib().mic_ce_bwd_w(_dt(logits), rows, V, Vpad, _p(logits), ld, _p(labels), _p(mask), _row_weight(row_weight, rows), float(ls),
+                                     _p(row_lse), _p(denom), float(loss_scale), _stream()), "mic_ce_bwd_w")
+        return
     L.check(L.lib().mic_ce_bwd(_dt(logits), rows, V, Vpad, _p(logits), ld, _p(labels), _p(mask), float(ls), _p(row_lse), _p(denom),
                                float(loss_scale), _stream()), "mic_ce_bwd")
 
@@ -430,9 +447,15 @@ def head_label_terms(labels, coef, E, h, dx_slab, dE, rows, width):
                                          _p(dE), dE.stride(0), _stream()), "mic_head_label_terms")
 
 
-def ce_bwd_t(logits, ld, V, Vpad, labels, mask, ls, row_lse, denom, rows, dlogits_t, rows_pad=0, colsum=None, loss_scale=1.0):
+def ce_bwd_t(logits, ld, V, Vpad, labels, mask, ls, row_lse, denom, rows, dlogits_t, rows_pad=0, colsum=None, loss_scale=1.0,
+             row_weight=None):
     """ce_bwd on bf16 logits that also writes dlogits^T [Vpad][ld_t] (columns rows .. rows_pad zero) and adds the column sums of the
-    stored gradient to `colsum` (mic_ce_bwd_t)"""
+    stored gradient to `colsum` (mic_ce_bwd_t); row_weight fp32 [rows]: the per-row loss weights of ce_bwd (mic_ce_bwd_t_w)"""
+    if row_weight is not None:
+        L.check(L.lib().mic_ce_bwd_t_w(rows, V, Vpad, _p(logits), ld, _p(labels), _p(mask), _row_weight(row_weight, rows), float(ls),
+                                       _p(row_lse), _p(denom), float(loss_scale), _p(dlogits_t), dlogits_t.stride(0), int(rows_pad),
+                                       _p(colsum), _stream()), "mic_ce_bwd_t_w")
+        return
     L.check(L.lib().mic_ce_bwd_t(rows, V, Vpad, _p(logits), ld, _p(labels), _p(mask), float(ls), _p(row_lse), _p(denom), float(loss_scale),
                                  _p(dlogits_t), dlogits_t.stride(0), int(rows_pad), _p(colsum), _stream()), "mic_ce_bwd_t")
 

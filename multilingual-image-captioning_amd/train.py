@@ -108,6 +108,36 @@ def check_captions_per_image(batch, fp8: bool = False) -> int:
     return G
 
 
+def check_loss_weights(batch, fp8: bool = False):
+    """batch["loss_weights"] (absent: None), checked on the host before anything touches a device: float weights of shape [R] (one
+    per caption row) or [R, T] (one per token), R, T = batch["input_ids"].shape; no fp8 GEMMs.  A host array must be finite and is
+    returned as a float32 numpy array; a device tensor is returned as it is — its shape is checked, its values are trusted (looking
+    at them would put a device-to-host sync into every step, like `packed_rows`)."""
+    w = batch.get("loss_weights")
+    if w is None:
+        return None
+    if fp8:
+        raise ValueError("batch['loss_weights'] is not supported together with gemm_dtype='fp8' (out of scope: the e5m2 dlogits of the "
+                         "fp8 LM head carry a closed-form scale that rests on |g| <= 1)")
+    R, T = (int(x) for x in batch["input_ids"].shape)
+    on_device = isinstance(w, torch.Tensor) and w.device.type != "cpu"
+    if not on_device:
+        w = w.numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
+        if w.dtype == object or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
+            raise ValueError(f"batch['loss_weights'] must hold real numbers, got dtype {w.dtype}")
+    elif not (w.is_floating_point() or w.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"batch['loss_weights'] must hold real numbers, got dtype {w.dtype}")
+    if tuple(w.shape) not in ((R,), (R, T)):
+        raise ValueError(f"batch['loss_weights'] must have shape [{R}] (one weight per caption row) or [{R}, {T}] (one per token), got "
+                         f"{list(w.shape)}")
+    if on_device:
+        return w
+    w = w.astype(np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError("batch['loss_weights'] holds non-finite values (NaN or inf)")
+    return w
+
+
 def plan_buckets(numel: int, bucket_elems: int, boundaries: List[int], max_elems: int = 0,
                  splittable: Tuple[Tuple[int, int, int], ...] = ()) -> List[Tuple[int, int]]:
     """Contiguous [begin, end) slices of the flat gradient buffer, cut at segment boundaries, each >= bucket_elems
@@ -977,6 +1007,7 @@ class Trainer:
         # several captions per image: G caption rows per image, image-major (refusals come before any device work)
         G = check_captions_per_image(batch, bool(getattr(m.engine, "fp8", False)))
         self._images = int(batch["pixel_values"].shape[0]) if G > 1 else None
+        lw = check_loss_weights(batch, bool(getattr(m.engine, "fp8", False)))
         px = m._dev(batch["pixel_values"], torch.float32)
         labels = m._dev(batch["input_ids"], torch.int32)
         mask = m._dev(batch["attention_mask"], torch.int32)
@@ -1023,6 +1054,13 @@ class Trainer:
             q_off, q_len, ids_p, pos_p = (m._dev(t, torch.int32) for t in pk)
             self._pack = ((q_off, q_len, rows[1]) + grouped, ids_p, pos_p)
         self._rows, self._row_labels = rows, row_labels
+        # per-caption / per-token loss weights -> one fp32 weight per head row: broadcast over T, gathered at the compacted head's rows
+        # (fresh tensors, fully written: nothing kept from an earlier step)
+        self._loss_kw = {}
+        if lw is not None:
+            w = m._dev(lw, torch.float32)
+            w = (w[:, None].expand(B, T) if w.dim() == 1 else w).reshape(-1)
+            self._loss_kw = dict(row_weights=torch.index_select(w, 0, rows[0]) if rows is not None else w.contiguous())
         return px, labels, mask, dec_in, pos, B, T
 
     def _set_hyper(self, lr: float, count: float) -> None:
@@ -1049,7 +1087,14 @@ class Trainer:
         """main.py:684-707.  batch["captions_per_image"] = G (optional, an int >= 1): `pixel_values` holds n_img images, the caption
         tensors (and "loss_rows" / "packed_rows") n_img * G rows, image-major — caption row r belongs to image r // G.  The step is the
         one on pixel_values.repeat_interleave(G, 0) with the image tower and the cross k/v projections run once per image; refused
-        (ValueError, before any device work): a G that is no int >= 1, caption rows != n_img * G, G > 1 with fp8 GEMMs."""
+        (ValueError, before any device work): a G that is no int >= 1, caption rows != n_img * G, G > 1 with fp8 GEMMs.
+        batch["loss_weights"] = w (optional; fp32 [R] per caption row or [R, T] per token, a host array or a device tensor; any finite
+        value, zeros and negatives included): loss = sum_{r,t} w[r,t] m[r,t] l[r,t] / sum_{r,t} m[r,t] with m the attention mask and
+        l the per-token loss (label smoothing included), and the gradients of that loss; "loss" in the metrics is this weighted loss.
+        The denominator is the number of valid tokens whatever w is — advantages may sum to zero, and a caption with w = 0 still counts
+        there (the mask drops it).  All weights 1.0 give the plain step bit for bit; without the key it is the plain step launch for
+        launch.  Refused (ValueError, before any device work): a shape other than [R] / [R, T], non-finite values in a host array (a
+        device tensor's values are trusted), fp8 GEMMs."""
         # (a micro-step that only accumulates issues no collective: the planner keeps all CUs there)
         budget = self._cu_budget if not (self.accumulate_steps > 1 and self._micro < self.accumulate_steps - 1) else 0
         if budget:
@@ -1109,11 +1154,11 @@ class Trainer:
                 if self._pack is not None:  # the decoder sees the valid positions only
                     pack, ids_p, pos_p = self._pack
                     loss = eng.loss_and_grads(px, ids_p, pos_p, None, labels.reshape(-1), B, T, label_smoothing=self.ls, seed=seed,
-                                              rows=self._rows, row_labels=self._row_labels, pack=pack, images=self._images)
+                                              rows=self._rows, row_labels=self._row_labels, pack=pack, images=self._images, **self._loss_kw)
                 else:
                     loss = eng.loss_and_grads(px, dec_in.reshape(-1), pos.reshape(-1), mask, labels.reshape(-1), B, T,
                                               label_smoothing=self.ls, seed=seed, rows=self._rows, row_labels=self._row_labels,
-                                              images=self._images)
+                                              images=self._images, **self._loss_kw)
             eng.on_embed_rows = None
             if not final:
                 r.finish()
@@ -1173,16 +1218,16 @@ class Trainer:
         return out
 
     def eval_step(self, batch: Dict) -> Dict[str, float]:
-        """main.py:710-721 (train=False, no dropout)."""
+        """main.py:710-721 (train=False, no dropout).  batch["loss_weights"]: the weighted loss of train_step."""
         m, eng = self.model, self.model.engine
         px, labels, mask, dec_in, pos, B, T = self._prep(batch)
         if self._pack is not None:
             pack, ids_p, pos_p = self._pack
             loss = eng.loss_only(px, ids_p, pos_p, None, labels.reshape(-1), B, T, label_smoothing=self.ls, rows=self._rows,
-                                 row_labels=self._row_labels, pack=pack, images=self._images)
+                                 row_labels=self._row_labels, pack=pack, images=self._images, **self._loss_kw)
         else:
             loss = eng.loss_only(px, dec_in.reshape(-1), pos.reshape(-1), mask, labels.reshape(-1), B, T, label_smoothing=self.ls,
-                                 rows=self._rows, row_labels=self._row_labels, images=self._images)
+                                 rows=self._rows, row_labels=self._row_labels, images=self._images, **self._loss_kw)
         self.metrics_buf[0:1].copy_(loss)
         self.metrics_buf[1:2].zero_()
         out = self._pmean_metrics()
